@@ -1,9 +1,17 @@
-"""bench.py -- BASELINE.json's headline: Mkeys/s sorting 2^30 uniform uint32 (k=8) on MI355X,
-plus the achieved HBM GB/s of the scatter pass against the roofline, and the reference's
-sequential sort (Baseline1.cu:15-64, oracle/_ref) timed on this host's cores beside it.
+"""bench.py -- BASELINE.json's headline: Mkeys/s sorting 2^30 uniform uint32 (k=8) on MI355X.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--n 1073741824] [--k 8]
-                  [--dist uniform|zipf] [--pairs] [--rank match|split] [--no-cpu]
+                  [--dist uniform|zipf] [--pairs] [--rank match|split] [--dump-outputs DIR]
+                  [--full [--no-cpu] [--no-vendor] [--no-e2e] [--configs c2,zipf,c4]]
+
+A plain run does what the headline needs and no more: it generates the input, warms up, times K
+steps, writes the last timed step's output under --dump-outputs, and prints one JSON line (metric,
+value, unit, higher_is_better, dtype, ms_per_step, the workload). --full adds everything else the
+line has carried, each measured in runs of its own after the timed steps: the on-device check of
+the timed output (`verified`), the achieved HBM GB/s of the scatter pass against the roofline and
+the per-phase times (a second set of K steps under HIP events), the rocPRIM column, the host->host
+time, BASELINE's other configurations, and the reference's sequential sort (Baseline1.cu:15-64,
+oracle/_ref) timed on this host's cores; for N > 1 the `multi` block.
 
 A step = one complete sort of the resident input (every pass: histogram, scan, fused local
 sort + scatter), device-resident: inputs are generated in HBM before timing, the timed region
@@ -61,6 +69,14 @@ def parse():
     ap.add_argument("--pairs", action="store_true")
     ap.add_argument("--rank", choices=["match", "split"], default="match")
     ap.add_argument("--tiles-per-chunk", type=int, default=0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (the sorted keys, the payloads "
+                         "with --pairs) as DIR/<name>.npy in float64; above a fixed size, the elements at a fixed, "
+                         "seeded sample of positions")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also check their output and measure the roofline, the phases, the "
+                         "vendor sort, the host->host time, the other configurations and the CPU baseline (the "
+                         "--no-* / --configs / --cpu-* options below choose among these)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--cpu-n", type=int, default=1 << 26, help="keys in the CPU-baseline headline sample")
     ap.add_argument("--cpu-reps", type=int, default=3)
@@ -87,7 +103,7 @@ def parse():
     ap.add_argument("--no-group-chunks", action="store_true",
                     help="every pass counts its own histogram (no digit-group chunks)")
     ap.add_argument("--configs", default="c2,zipf,c4",
-                    help="BASELINE configurations measured after the headline in the same process, "
+                    help="--full: BASELINE configurations measured after the headline in the same process, "
                          "reported in the line's `configs` block ('' for none; N=1 only): " + ", ".join(CONFIGS))
     ap.add_argument("--configs-n", type=int, default=0, help="override every config's key count (tests)")
     ap.add_argument("--configs-reps", type=int, default=7, help="timed sorts per config (median)")
@@ -579,6 +595,27 @@ def multi_summary(per_rank, world, rank_of_stats, transport, sc, pt, steps):
     }
 
 
+DUMP_ELEMENTS = 6 << 20  # --dump-outputs: float64 elements over all files of a run (48 MiB)
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(dirname, arrays, rank, world):
+    """--dump-outputs: the arrays the last timed step returned (name -> device u32 tensor, None
+    skipped) as DIR/<name>.npy, float64 (every u32 exactly); N > 1: DIR/<name>_rank<r>.npy, each
+    rank its own slice. An array longer than its share of DUMP_ELEMENTS is dumped at a sample of
+    positions, ascending, drawn from its length and DUMP_SEED alone: the same in every run and build."""
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    arrays = {name: t for name, t in arrays.items() if t is not None}
+    cap = DUMP_ELEMENTS // (len(arrays) * world)
+    for name, t in arrays.items():
+        m = t.numel()
+        if m > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, m, size=cap, dtype=np.int64))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(d / (name + (f"_rank{rank}" if world > 1 else "") + ".npy"), rs.to_numpy_u32(t).astype(np.float64))
+
+
 def main():
     a = parse()
     # --gpus N without a launcher: start the N ranks here (before anything touches the GPU)
@@ -637,7 +674,7 @@ def main():
     if a.pairs:
         vals = rs.empty_u32(n, dev)
         rs.gen_iota(vals, rank * n)
-    fp_in = rs.fingerprint(keys, vals)[0]
+    fp_in = rs.fingerprint(keys, vals)[0] if a.full else None
     p = rs.plan(n, a.k, a.pairs, a.tiles_per_chunk)
 
     comm = None
@@ -704,6 +741,55 @@ def main():
     if world > 1:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el.item())
+    if a.dump_outputs:
+        ok, ov = res["out"][:2] if use_dist else (out, vout)
+        dump_outputs(a.dump_outputs, {"keys": ok, "values": ov}, rank, world)
+        del ok, ov
+
+    def close():
+        if host_tr is not None:
+            barrier()
+            host_tr.close()
+        if comm is not None and host_tr is None:
+            comm.close()
+        if use_dist:
+            dist.destroy_process_group()
+
+    # the headline: all a plain run prints; --full adds its blocks to this line below
+    line = {
+        "metric": "Mkeys/s sorting 2^30 uniform uint32; scatter-pass achieved HBM GB/s",
+        "value": round(n * world * a.steps / elapsed / 1e6, 1),
+        "unit": "Mkeys/s",
+        "n_gpus": world,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": round(elapsed / a.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u32",
+        "data": {"uniform": "synthetic (splitmix64 uniform u32, seed 0x5EED, generated in HBM)",
+                 "zipf": "synthetic (Zipf s=1.0 over 2^20 ranks, key=fmix32(rank))",
+                 "zipf12": "synthetic (Zipf s=1.2 over 2^20 ranks, key=fmix32(rank))",
+                 "hot": "synthetic (uniform u32, a quarter of the positions set to 0x00C0FFEE)",
+                 "equal": "synthetic (every key 0x01234567)"}[a.dist],
+        "config": {"workload": f"sort {n} {'key+value pairs' if a.pairs else 'uint32 keys'} per GPU, "
+                               f"k={a.k} ({p.passes} passes), {a.dist}"
+                               + (f"; {world} ranks, key-range partition + one exchange + local sort"
+                                  if use_dist else ""),
+                   "keys_per_gpu": n, "k_bits": a.k, "passes": p.passes, "dist": a.dist,
+                   "pairs": bool(a.pairs), "rank_algo": a.rank, "tile_keys": p.tile_keys,
+                   "tiles_per_chunk": p.tiles_per_chunk, "num_chunks": p.num_chunks,
+                   "parallelism": "single GPU" if not use_dist else
+                   f"range-partition x{world} ({transport}"
+                   f"{', full protocol' if a.dist_full and a.dist_impl == 'c' else ''})"},
+    }
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        close()
+        return
+
     # per-phase HIP events in a second, separate set of steps: the event records between the
     # phases cost ~10 us each (~85 us per C3 sort, rocprofv3 kernel trace), so `value` is timed
     # without them and the roofline's per-launch kernel times come from these steps; the multi-GPU
@@ -828,7 +914,6 @@ def main():
         cpu = cpu_baseline(host_keys, min(a.cpu_n, n), a.k, a.cpu_reps, a.dist, rows)
 
     if rank == 0:
-        total_keys = n * world * a.steps
         roof = {"bound": "hbm", "kernel": f"{kernel} (fused local sort + rank + scatter"
                                           f"{'; the local sort after the exchange' if use_dist else ''})",
                 "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -849,52 +934,30 @@ def main():
                 roof["avg_launch_ms_rocprof_csv"] = round(rc, 4)
                 roof["frac_rocprof_csv"] = round(algo_bytes / (rc * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
                 roof["rocprof_csv_source"] = prec.get("rocprof_csv_source")
-        line = {
-            "metric": "Mkeys/s sorting 2^30 uniform uint32; scatter-pass achieved HBM GB/s",
-            "value": round(total_keys / elapsed / 1e6, 1),
-            "unit": "Mkeys/s",
-            "n_gpus": world,
-            "steps": a.steps,
-            "warmup": a.warmup,
-            "ms_per_step": round(elapsed / a.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u32",
-            "data": {"uniform": "synthetic (splitmix64 uniform u32, seed 0x5EED, generated in HBM)",
-                     "zipf": "synthetic (Zipf s=1.0 over 2^20 ranks, key=fmix32(rank))",
-                     "zipf12": "synthetic (Zipf s=1.2 over 2^20 ranks, key=fmix32(rank))",
-                     "hot": "synthetic (uniform u32, a quarter of the positions set to 0x00C0FFEE)",
-                     "equal": "synthetic (every key 0x01234567)"}[a.dist],
-            "config": {"workload": f"sort {n} {'key+value pairs' if a.pairs else 'uint32 keys'} per GPU, "
-                                   f"k={a.k} ({p.passes} passes), {a.dist}"
-                                   + (f"; {world} ranks, key-range partition + one exchange + local sort"
-                                      if use_dist else ""),
-                       "keys_per_gpu": n, "k_bits": a.k, "passes": p.passes, "dist": a.dist,
-                       "pairs": bool(a.pairs), "rank_algo": a.rank, "tile_keys": p.tile_keys,
-                       "tiles_per_chunk": p.tiles_per_chunk, "num_chunks": p.num_chunks,
-                       "group_chunk_passes": ([2 * i + 1 for i, f in enumerate(groups) if f]
-                                              if groups is not None else None),
-                       # per odd pass: its digit groups, equal chunks cutting unbalanced groups, or
-                       # fixed chunks with a counted histogram (rsort_group_flags)
-                       "group_chunk_modes": ([("fixed", "groups", "cut")[f] for f in groups]
-                                             if groups is not None else None),
-                       # the scatter instantiations the library's dispatch launched in the timed
-                       # steps (rsort_scatter_kernels_used), and the ranking the probe allowed
-                       "scatter_kernels": kernels_used,
-                       "lane_order_probe": probe,
-                       "ranking": ("lane-ordered returning LDS adds (kRankAtomic)" if probe == 1 and a.rank == "match"
-                                   else "wave64 ballot peer match (kRankCount)" if a.rank == "match"
-                                   else "k 1-bit splits (kRankSplit)"),
-                       "parallelism": "single GPU" if not use_dist else
-                       f"range-partition x{world} ({transport}"
-                       f"{', overlap' if a.dist_impl == 'c' and prof_c and multi_stats and multi_stats[-1]['halves'] == 2 else ''}"
-                       f"{', full protocol' if a.dist_full and a.dist_impl == 'c' else ''})"},
+        line["config"].update({
+            "group_chunk_passes": ([2 * i + 1 for i, f in enumerate(groups) if f]
+                                   if groups is not None else None),
+            # per odd pass: its digit groups, equal chunks cutting unbalanced groups, or
+            # fixed chunks with a counted histogram (rsort_group_flags)
+            "group_chunk_modes": ([("fixed", "groups", "cut")[f] for f in groups]
+                                  if groups is not None else None),
+            # the scatter instantiations the library's dispatch launched in the timed and the
+            # profiled steps (rsort_scatter_kernels_used), and the ranking the probe allowed
+            "scatter_kernels": kernels_used,
+            "lane_order_probe": probe,
+            "ranking": ("lane-ordered returning LDS adds (kRankAtomic)" if probe == 1 and a.rank == "match"
+                        else "wave64 ballot peer match (kRankCount)" if a.rank == "match"
+                        else "k 1-bit splits (kRankSplit)"),
+            "parallelism": "single GPU" if not use_dist else
+            f"range-partition x{world} ({transport}"
+            f"{', overlap' if a.dist_impl == 'c' and prof_c and multi_stats and multi_stats[-1]['halves'] == 2 else ''}"
+            f"{', full protocol' if a.dist_full and a.dist_impl == 'c' else ''})"})
+        line.update({
             "verified": bool(verified),
             "roofline": roof,
             "phases_ms_per_step": {"histogram": round(hi["ms"] / a.steps, 4), "scan": round(scan["ms"] / a.steps, 4),
                                    "scatter": round(sc["ms"] / a.steps, 4)},
-        }
+        })
         if use_dist and prof_c:
             line["multi"] = multi_summary(per_rank_stats, world, {"rccl_world": rccl_world}, transport, sc,
                                           prof.times["partition"], a.steps)
@@ -907,13 +970,7 @@ def main():
         if cpu is not None:
             line["cpu_baseline"] = cpu
         print(json.dumps(line), flush=True)
-    if host_tr is not None:
-        barrier()
-        host_tr.close()
-    if comm is not None and host_tr is None:
-        comm.close()
-    if use_dist:
-        dist.destroy_process_group()
+    close()
 
 
 if __name__ == "__main__":

@@ -69,7 +69,7 @@ kt() {  # tag, bench args...
     shift
     rm -rf "$R/gpurun_out/kt_$tag"
     (cd /tmp && TMPDIR=/tmp timeout -k 10 200 rocprofv3 --kernel-trace --output-format csv -d "$R/gpurun_out/kt_$tag" -- \
-        python3 "$R/bench.py" --no-cpu --no-e2e --no-vendor --configs "" --steps 2 --warmup 1 "$@" \
+        python3 "$R/bench.py" --full --no-cpu --no-e2e --no-vendor --configs "" --steps 2 --warmup 1 "$@" \
         > "$R/gpurun_out/kt_$tag.log" 2>&1)
     stop_unless_ok $? "kt $tag"
 }
@@ -87,7 +87,7 @@ floors)
     stop_unless_ok $? "ceiling c2"
     timeout -k 10 200 dev/ceiling_lab 30 10 pairs >> gpurun_out/floors.jsonl 2>> gpurun_out/floors.err
     stop_unless_ok $? "ceiling pairs"
-    run_bench floors_bench --steps 10 --warmup 3 --no-cpu --no-vendor --no-e2e --configs c2,c4 > /dev/null
+    run_bench floors_bench --full --steps 10 --warmup 3 --no-cpu --no-vendor --no-e2e --configs c2,c4 > /dev/null
     grep -h '"pass"\|c2_\|runs32_pairs\|runs64"' gpurun_out/floors.jsonl
     ;;
 partab)
@@ -110,7 +110,7 @@ round)
         > gpurun_out/round_tests.log 2>&1
     ok_or_stop $? pytest
     tail -n 3 gpurun_out/round_tests.log
-    run_bench round_bench --steps 20 --warmup 5
+    run_bench round_bench --full --steps 20 --warmup 5
     ;;
 tests)
     timeout -k 10 900 python -u -m pytest tests -m gpu -v --maxfail 8 --timeout 300 --timeout-method thread "$@" \
@@ -130,8 +130,8 @@ pairs)
         --timeout 300 --timeout-method thread > gpurun_out/pairs_tests.log 2>&1
     ok_or_stop $? pytest
     grep -E "passed|failed|FAILED|Error" gpurun_out/pairs_tests.log | tail -n 12
-    run_bench pairs_new --steps 5 --warmup 2 --keys 16777216 --no-cpu --no-vendor --no-e2e --configs c4,zipf "$@"
-    RSORT_LAB=1 RSORT_PAIRS64=1 run_bench pairs_64 --steps 5 --warmup 2 --keys 16777216 --no-cpu --no-vendor --no-e2e \
+    run_bench pairs_new --full --steps 5 --warmup 2 --keys 16777216 --no-cpu --no-vendor --no-e2e --configs c4,zipf "$@"
+    RSORT_LAB=1 RSORT_PAIRS64=1 run_bench pairs_64 --full --steps 5 --warmup 2 --keys 16777216 --no-cpu --no-vendor --no-e2e \
         --configs c4 "$@"
     ;;
 pairslab)
@@ -147,7 +147,7 @@ pairslab)
     ;;
 cl)
     for v in 2 1; do
-        RSORT_CL=$v run_bench "cl$v" --steps 2 --warmup 1 --keys 16777216 --no-cpu --no-vendor --no-e2e \
+        RSORT_CL=$v run_bench "cl$v" --full --steps 2 --warmup 1 --keys 16777216 --no-cpu --no-vendor --no-e2e \
             --configs zipf,c4 "$@" > /dev/null
         python3 - "$v" <<'PY'
 import json, sys
@@ -198,7 +198,7 @@ ab)
         if [ "$side" = new ]; then cp gpurun_out/ab_new.so cuda.radixsort_amd/librsort.so; else cp "dev/var_$v.so" cuda.radixsort_amd/librsort.so; fi
         # (the variant may predate symbols radixsort.py binds: RSORT_LAB_OLD_LIB leaves those unbound)
         if [ "$side" = new ]; then oldlib=0; else oldlib=1; fi
-        RSORT_LAB=1 RSORT_LAB_OLD_LIB=$oldlib run_bench "ab_$side" --steps 10 --warmup 3 --no-cpu --no-vendor --no-e2e \
+        RSORT_LAB=1 RSORT_LAB_OLD_LIB=$oldlib run_bench "ab_$side" --full --steps 10 --warmup 3 --no-cpu --no-vendor --no-e2e \
             --configs "${2:-zipf,c4}" > /dev/null
         python3 - "$side" <<'PY'
 import json, sys
@@ -220,10 +220,10 @@ envab)
     kv=$1
     for side in new env new env; do
         if [ "$side" = env ]; then
-            env $kv timeout -k 10 300 python bench.py --steps 10 --warmup 3 --no-cpu --no-vendor --no-e2e \
+            env $kv timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --no-cpu --no-vendor --no-e2e \
                 --configs "${2:-c2}" > gpurun_out/envab_$side.json 2> gpurun_out/envab_$side.err
         else
-            timeout -k 10 300 python bench.py --steps 10 --warmup 3 --no-cpu --no-vendor --no-e2e \
+            timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --no-cpu --no-vendor --no-e2e \
                 --configs "${2:-c2}" > gpurun_out/envab_$side.json 2> gpurun_out/envab_$side.err
         fi
         stop_unless_ok $? "envab $side"
@@ -254,7 +254,7 @@ sqpmc)
             -d "$R/gpurun_out/sqpmc_pairs_$i" -- "$R/dev/pairs_lab" 29 > "$R/gpurun_out/sqpmc_pairs_$i.log" 2>&1)
         stop_unless_ok $? "sqpmc pairs $i"
         (cd /tmp && TMPDIR=/tmp timeout -s KILL 120 rocprofv3 --pmc $P --output-format csv -d "$R/gpurun_out/sqpmc_keys_$i" -- \
-            python3 "$R/bench.py" --keys 536870912 --steps 1 --warmup 1 --no-cpu --no-e2e --no-vendor --configs "" \
+            python3 "$R/bench.py" --full --keys 536870912 --steps 1 --warmup 1 --no-cpu --no-e2e --no-vendor --configs "" \
             > "$R/gpurun_out/sqpmc_keys_$i.log" 2>&1)
         stop_unless_ok $? "sqpmc keys $i"
     done
@@ -273,7 +273,7 @@ sqc2)
             tag=${cfg%%:*}
             rm -rf "$R/gpurun_out/sqpmc_${tag}_$i"
             (cd /tmp && TMPDIR=/tmp timeout -s KILL 120 rocprofv3 --pmc $P --output-format csv -d "$R/gpurun_out/sqpmc_${tag}_$i" -- \
-                python3 "$R/bench.py" ${cfg#*:} --steps 1 --warmup 1 --no-cpu --no-e2e --no-vendor --configs "" \
+                python3 "$R/bench.py" --full ${cfg#*:} --steps 1 --warmup 1 --no-cpu --no-e2e --no-vendor --configs "" \
                 > "$R/gpurun_out/sqpmc_${tag}_$i.log" 2>&1)
             stop_unless_ok $? "sqc2 $tag $i"
         done
@@ -286,7 +286,7 @@ sqzipf)
     P1="SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_LDS SQ_INSTS_LDS SQ_LDS_ADDR_CONFLICT SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_SALU"
     rm -rf "$R/gpurun_out/sqzipf_keys_1"
     (cd /tmp && TMPDIR=/tmp timeout -s KILL 120 rocprofv3 --pmc $P1 --output-format csv -d "$R/gpurun_out/sqzipf_keys_1" -- \
-        python3 "$R/bench.py" --keys 536870912 --dist zipf --steps 1 --warmup 1 --no-cpu --no-e2e --no-vendor --configs "" \
+        python3 "$R/bench.py" --full --keys 536870912 --dist zipf --steps 1 --warmup 1 --no-cpu --no-e2e --no-vendor --configs "" \
         > "$R/gpurun_out/sqzipf_keys_1.log" 2>&1)
     stop_unless_ok $? "sqzipf"
     python3 dev/sqpmc.py gpurun_out --order sqzipf_keys
@@ -314,7 +314,7 @@ c2tpc)
     for rep in 1 2; do
         for tpc in ${C2_TPCS:-16 8 4}; do
             for tail in 0 1; do
-                RSORT_LAB=1 RSORT_NX_TAIL=$tail timeout -k 10 120 python bench.py --keys 67108864 --k 4 --tiles-per-chunk $tpc \
+                RSORT_LAB=1 RSORT_NX_TAIL=$tail timeout -k 10 120 python bench.py --full --keys 67108864 --k 4 --tiles-per-chunk $tpc \
                     --steps 20 --warmup 5 --no-cpu --no-vendor --no-e2e --configs "" > gpurun_out/c2tpc.json 2> gpurun_out/c2tpc.err
                 stop_unless_ok $? "c2 tpc=$tpc tail=$tail" > /dev/null
                 python3 - "$tpc" "$tail" <<'PY'
@@ -367,7 +367,7 @@ pfloor)
     stop_unless_ok $? pfloor
     cat gpurun_out/pfloor.jsonl
     for d in uniform zipf; do
-        timeout -k 10 200 python bench.py --dist $d --pairs --steps 10 --warmup 3 --no-cpu --no-vendor --no-e2e \
+        timeout -k 10 200 python bench.py --full --dist $d --pairs --steps 10 --warmup 3 --no-cpu --no-vendor --no-e2e \
             --configs "" > gpurun_out/pfloor_$d.json 2> gpurun_out/pfloor_$d.err
         stop_unless_ok $? "pfloor $d"
         python3 - "$d" <<'PY'
@@ -403,10 +403,10 @@ cutw)
                     "--dist hot --pairs"; do
             for w in 1 0; do
                 if [ $w = 1 ]; then
-                    timeout -k 10 200 python bench.py $args --steps 10 --warmup 3 --no-cpu --no-vendor --no-e2e --configs "" \
+                    timeout -k 10 200 python bench.py --full $args --steps 10 --warmup 3 --no-cpu --no-vendor --no-e2e --configs "" \
                         > gpurun_out/cutw.json 2> gpurun_out/cutw.err
                 else
-                    RSORT_LAB=1 RSORT_CUT_WEIGHTS=0 timeout -k 10 200 python bench.py $args --steps 10 --warmup 3 --no-cpu \
+                    RSORT_LAB=1 RSORT_CUT_WEIGHTS=0 timeout -k 10 200 python bench.py --full $args --steps 10 --warmup 3 --no-cpu \
                         --no-vendor --no-e2e --configs "" > gpurun_out/cutw.json 2> gpurun_out/cutw.err
                 fi
                 stop_unless_ok $? "cutw $args w=$w" > /dev/null
@@ -440,6 +440,7 @@ dist)
     rm -rf "$R/gpurun_out/prof_dist"
     (cd /tmp && TMPDIR=/tmp timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv \
         -d "$R/gpurun_out/prof_dist" -- python3 "$R/bench.py" --no-cpu --no-e2e --configs "" --dist-path \
+        --full \
         --steps 3 --warmup 1 "$@" > "$R/gpurun_out/prof_dist.log" 2>&1)
     stop_unless_ok $? dist
     tail -c 1500 "$R/gpurun_out/prof_dist.log"
@@ -454,7 +455,7 @@ profiles)
         d="$R/gpurun_out/prof_${tag}_dist${v:+_full}"
         rm -rf "$d"
         (cd /tmp && TMPDIR=/tmp timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$d" -- \
-            python3 "$R/bench.py" --no-cpu --no-e2e --no-vendor --configs "" --dist-path $v --steps 3 --warmup 1 \
+            python3 "$R/bench.py" --full --no-cpu --no-e2e --no-vendor --configs "" --dist-path $v --steps 3 --warmup 1 \
             > "$d.log" 2>&1)
         stop_unless_ok $? "dist $v"
         tail -c 600 "$d.log"

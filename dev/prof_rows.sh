@@ -7,6 +7,7 @@ for v in 1 0; do
     rm -rf "$R/gpurun_out/prows$v"
     (cd /tmp && RSORT_LAB=1 RSORT_PIECE_ROWS=$v TMPDIR=/tmp timeout -k 10 200 rocprofv3 --kernel-trace --output-format csv \
         -d "$R/gpurun_out/prows$v" -- python3 "$R/bench.py" --keys 1073741824 --dist ${DIST:-zipf} ${PAIRS:-} --steps 4 \
+        --full \
         --warmup 1 --no-cpu --no-vendor --no-e2e --configs "" > "$R/gpurun_out/prows$v.log" 2>&1) || exit 1
 done
 for v in 1 0; do

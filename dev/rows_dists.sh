@@ -7,7 +7,7 @@ mkdir -p gpurun_out
 for rep in 1 2; do
     for args in "--dist hot" "--dist zipf12" "--dist zipf --keys 268435456" "--dist hot --pairs"; do
         for v in 1 0; do
-            RSORT_LAB=1 RSORT_PIECE_ROWS=$v timeout -k 10 200 python bench.py $args --steps 10 --warmup 3 --no-cpu \
+            RSORT_LAB=1 RSORT_PIECE_ROWS=$v timeout -k 10 200 python bench.py --full $args --steps 10 --warmup 3 --no-cpu \
                 --no-vendor --no-e2e --configs "" > gpurun_out/rows_dists.json 2> gpurun_out/rows_dists.err || exit 1
             python3 - "$v" "$args" <<'PY' >> gpurun_out/rows_dists.log
 import json, sys

@@ -68,6 +68,44 @@ def test_gpus2_without_enough_gpus_fails_fast_with_a_message():
     assert r.returncode == 2 and "GPU(s) visible" in r.stderr, (r.returncode, r.stderr[-1000:])
 
 
+def test_full_and_dump_outputs_are_off_by_default(monkeypatch):
+    bench = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and (a.gpus, a.steps, a.warmup) == (1, 4, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_whole_below_the_limit_and_a_fixed_sample_above(tmp_path):
+    """dump_outputs on host tensors: float64 files of the u32 bits; an array within its share of
+    DUMP_ELEMENTS whole, a longer one at positions that depend on its length and DUMP_SEED alone;
+    all files of a run within 64 MB; per-rank names for N > 1."""
+    import numpy as np
+    import torch
+    bench = _bench()
+    small = torch.arange(-5, 1000, dtype=torch.int32)  # (negative int32: u32 keys above 2^31)
+    bench.dump_outputs(tmp_path / "s", {"keys": small, "values": None}, 0, 1)
+    assert [f.name for f in (tmp_path / "s").iterdir()] == ["keys.npy"]
+    got = np.load(tmp_path / "s" / "keys.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, small.numpy().view(np.uint32).astype(np.float64))
+    assert got[0] == 2.0 ** 32 - 5
+    m = bench.DUMP_ELEMENTS + 12345
+    big = torch.arange(m, dtype=torch.int32)
+    for sub in ("x", "y"):
+        bench.dump_outputs(tmp_path / sub, {"keys": big, "values": big}, 0, 1)
+    files = sorted((tmp_path / "x").iterdir())
+    assert [f.name for f in files] == ["keys.npy", "values.npy"]
+    assert sum(f.stat().st_size for f in files) <= 64 * 10 ** 6
+    k = np.load(files[0])
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, m, size=bench.DUMP_ELEMENTS // 2, dtype=np.int64))
+    assert np.array_equal(k, idx.astype(np.float64)) and np.array_equal(np.load(files[1]), k)
+    assert np.array_equal(np.load(tmp_path / "y" / "keys.npy"), k)
+    bench.dump_outputs(tmp_path / "r", {"keys": small}, 3, 4)
+    assert [f.name for f in (tmp_path / "r").iterdir()] == ["keys_rank3.npy"]
+
+
 def test_launch_timeout_default_scales_with_the_job():
     bench = _bench()
 

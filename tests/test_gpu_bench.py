@@ -6,19 +6,66 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
 
 
-def run_bench(*args):
+def run_plain(*args):
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), *args], capture_output=True, text=True,
                        timeout=240, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
     return json.loads(lines[0])
+
+
+def run_bench(*args):
+    """The whole line (`verified`, roofline, phases, configs, vendor, CPU rows, `multi`): --full."""
+    return run_plain("--full", *args)
+
+
+PLAIN_KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config"}
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_output(tmp_path):
+    """A plain run prints the headline and nothing that takes a run of its own; --dump-outputs writes
+    the last timed sort's keys, float64: the sorted input exactly, so the same file in every run."""
+    from _util import uniform_keys
+    n = (1 << 20) + 77  # (below the dump's sample size: the whole output)
+    d = run_plain("--gpus", "1", "--steps", "3", "--warmup", "1", "--keys", str(n), "--dump-outputs", str(tmp_path / "a"))
+    assert set(d) == PLAIN_KEYS, sorted(d)
+    assert d["unit"] == "Mkeys/s" and d["higher_is_better"] is True and d["dtype"] == "u32"
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1
+    # value and ms_per_step are one measurement (ms_per_step is rounded to 1e-3 ms, value to 0.1)
+    assert d["ms_per_step"] > 0
+    assert abs(d["value"] - n / (d["ms_per_step"] * 1e-3) / 1e6) <= d["value"] * 0.0006 / d["ms_per_step"] + 0.1
+    assert d["config"]["keys_per_gpu"] == n and d["config"]["parallelism"] == "single GPU"
+    assert sorted(f.name for f in (tmp_path / "a").iterdir()) == ["keys.npy"]
+    got = np.load(tmp_path / "a" / "keys.npy")
+    assert got.dtype == np.float64 and got.shape == (n,)
+    assert np.array_equal(got, np.sort(uniform_keys(n, seed=0x5EED)).astype(np.float64))
+
+
+def test_bench_dump_outputs_pairs_sampled(tmp_path):
+    """Above the size limit the dump is the output at a fixed sample of positions (its length and a
+    fixed seed alone), keys and payloads at the same ones; under --full too, beside the whole line."""
+    import bench
+    from _util import oracle_sort_pairs, zipf_keys
+    n = (1 << 22) + 5
+    d = run_bench("--steps", "1", "--warmup", "1", "--keys", str(n), "--dist", "zipf", "--pairs", "--no-cpu",
+                  "--no-vendor", "--no-e2e", "--configs", "", "--dump-outputs", str(tmp_path))
+    assert d["verified"] is True and PLAIN_KEYS < set(d)
+    cap = bench.DUMP_ELEMENTS // 2
+    assert cap < n and 8 * bench.DUMP_ELEMENTS <= 64 * 10 ** 6
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, n, size=cap, dtype=np.int64))
+    rk, rv = oracle_sort_pairs(zipf_keys(n, seed=0x5EED), np.arange(n, dtype=np.uint32), 8)
+    k, v = np.load(tmp_path / "keys.npy"), np.load(tmp_path / "values.npy")
+    assert k.dtype == np.float64 and v.dtype == np.float64
+    assert np.array_equal(k, rk[idx].astype(np.float64)) and np.array_equal(v, rv[idx].astype(np.float64))
 
 
 def test_bench_headline_contract():
@@ -88,7 +135,7 @@ def run_bench_env(env_extra, *args, timeout=300):
     import os
     env = dict(os.environ)
     env.update(env_extra)
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), *args], capture_output=True, text=True,
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", *args], capture_output=True, text=True,
                        timeout=timeout, cwd=str(ROOT), env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
