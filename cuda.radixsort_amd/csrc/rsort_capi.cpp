@@ -635,6 +635,153 @@ int host_sort(const uint32_t *kin, const uint32_t *vin, uint32_t *kout, uint32_t
     return check ? RSORT_ERR_CHECK : RSORT_OK;
 }
 
+// ------------------------------------------------------------------------------ segmented sort
+// Workspace of rsort_u32_segmented_device: the multi-tile path's ping-pong keys (and values), one list per kernel
+// kind (room for every segment in each: the kinds are only known on the device) and the counters.
+struct SegCarve {
+    uint32_t *ktmp, *vtmp, *lists[kSegKinds], *counters;
+    size_t bytes;
+};
+
+SegCarve seg_carve(int64_t n, int64_t nseg, int pairs, void *ws) {
+    SegCarve c;
+    char *q = (char *)ws;
+    size_t o = 0;
+    c.ktmp = (uint32_t *)(q + o);
+    o += align256((size_t)n * 4);
+    c.vtmp = pairs ? (uint32_t *)(q + o) : nullptr;
+    if (pairs) o += align256((size_t)n * 4);
+    for (int i = 0; i < kSegKinds; ++i) {
+        c.lists[i] = (uint32_t *)(q + o);
+        o += align256((size_t)nseg * 4);
+    }
+    c.counters = (uint32_t *)(q + o);
+    o += 256;
+    c.bytes = o;
+    return c;
+}
+
+bool seg_sizes_ok(int64_t n, int64_t nseg, int *st) {
+    *st = RSORT_OK;
+    if (n < 0 || n >= ((int64_t)1 << 32)) *st = RSORT_ERR_SIZE;
+    else if (nseg < 0 || nseg >= ((int64_t)1 << 31)) *st = RSORT_ERR_ARG;
+    return *st == RSORT_OK;
+}
+
+int seg_sort(const uint32_t *kin, const uint32_t *vin, uint32_t *kout, uint32_t *vout, int64_t n,
+             const uint32_t *off, int64_t nseg, void *ws, size_t ws_bytes, hipStream_t s) {
+    int st;
+    if (!seg_sizes_ok(n, nseg, &st)) return st;
+    if ((vin != nullptr) != (vout != nullptr)) return RSORT_ERR_ARG;
+    if (n == 0 || nseg == 0) return RSORT_OK;
+    if (!kin || !kout || !off || !ws) return RSORT_ERR_ARG;
+    if (!aligned4(kin) || !aligned4(kout) || !aligned4(vin) || !aligned4(vout) || !aligned4(off) || !aligned4(ws))
+        return RSORT_ERR_ALIGN;
+    const int pairs = vin != nullptr;
+    const SegCarve c = seg_carve(n, nseg, pairs, ws);
+    if (ws_bytes < c.bytes) return RSORT_ERR_WORKSPACE;
+
+    const int rank = internal_rank(g_rank_algo.load()) == kRankAtomic ? kRankAtomic : kRankCount;
+    if (hipMemsetAsync(c.counters, 0, 256, s) != hipSuccess) return RSORT_ERR_HIP;
+    {
+        PhaseScope ps(RSORT_PHASE_HISTOGRAM, nseg, s);
+        SegClassifyArgs a{};
+        a.off = off;
+        for (int i = 0; i < kSegKinds; ++i) a.lists[i] = c.lists[i];
+        a.counters = c.counters;
+        a.n = (uint64_t)n;
+        a.num_segments = (uint32_t)nseg;
+        if ((st = hip_status(launch_seg_classify(a, s)))) return st;
+    }
+    // The lists' lengths are only known on the device: every kernel is launched with a grid from the segment
+    // count, the CU count and its occupancy, and one whose list is empty returns at once.
+    const int cus = std::max(1, device_cus());
+    for (int kind = 0; kind < kSegKinds; ++kind) {
+        // the most segments the kind can have: each holds more keys than the kind below takes; a wave-kind
+        // workgroup sorts four segments at a time
+        const int below = kind == kSegSmall ? kSegWaveKeys : kind == kSegLds ? kSegSmallKeys : kind == kSegTiles ? kSegLdsKeys : 0;
+        int64_t most = below ? std::min<int64_t>(nseg, n / below) : nseg;
+        if (kind == kSegWave) most = (most + 3) / 4;
+        if (most == 0) continue;
+        const int bpc = std::max(1, seg_blocks_per_cu(kind, pairs, rank));
+        const uint32_t grid = (uint32_t)std::min<int64_t>(most, (int64_t)cus * bpc * 4);
+        PhaseScope ps(RSORT_PHASE_SCATTER, n, s);
+        SegSortArgs a{};
+        a.kin = kin;
+        a.vin = vin;
+        a.kout = kout;
+        a.vout = vout;
+        a.ktmp = c.ktmp;
+        a.vtmp = c.vtmp;
+        a.off = off;
+        a.list = c.lists[kind];
+        a.count = c.counters + kind;
+        a.check = c.counters + kSegCheckWord;
+        a.rank_fault = g_rank_fault.load() ? 1u : 0u;
+        if ((st = hip_status(launch_seg_sort(kind, pairs, rank, a, grid, s)))) return st;
+    }
+    return RSORT_OK;
+}
+
+int seg_host_sort(const uint32_t *kin, const uint32_t *vin, uint32_t *kout, uint32_t *vout, int64_t n,
+                  const uint32_t *off, int64_t nseg) {
+    int st;
+    if (!seg_sizes_ok(n, nseg, &st)) return st;
+    if ((vin != nullptr) != (vout != nullptr)) return RSORT_ERR_ARG;
+    if (n == 0 || nseg == 0) return RSORT_OK;
+    if (!kin || !kout || !off) return RSORT_ERR_ARG;
+    for (int64_t i = 0; i < nseg; ++i)
+        if (off[i] > off[i + 1] || (int64_t)off[i + 1] > n) return RSORT_ERR_ARG;
+    const int pairs = vin != nullptr;
+    int count = 0, dev = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return RSORT_ERR_NODEV;
+    if (hipGetDevice(&dev) != hipSuccess) return RSORT_ERR_HIP;
+    // the segments are contiguous: together they cover [lo, lo + m), and only that range travels
+    const size_t lo = off[0], m = (size_t)off[nseg] - off[0];
+    if (m == 0) return RSORT_OK;
+    DevCache *dc = cache_for(dev);
+    std::lock_guard<std::mutex> g(dc->mu);
+    const size_t nb = align256((size_t)n * 4), ob = align256((size_t)(nseg + 1) * 4);
+    const size_t wsb = seg_carve(n, nseg, pairs, nullptr).bytes;
+    const size_t need = nb * (pairs ? 4 : 2) + ob + wsb;
+    if (!dc->stream && hipStreamCreateWithFlags(&dc->stream, hipStreamNonBlocking) != hipSuccess)
+        return RSORT_ERR_HIP;
+    if (dc->cap < need) {
+        if (dc->buf) (void)hipFree(dc->buf);
+        dc->buf = nullptr;
+        dc->cap = 0;
+        if (hipMalloc(&dc->buf, need) != hipSuccess) return RSORT_ERR_ALLOC;
+        dc->cap = need;
+    }
+    char *q = (char *)dc->buf;
+    uint32_t *d_kin = (uint32_t *)q;
+    uint32_t *d_kout = (uint32_t *)(q + nb);
+    uint32_t *d_vin = pairs ? (uint32_t *)(q + 2 * nb) : nullptr;
+    uint32_t *d_vout = pairs ? (uint32_t *)(q + 3 * nb) : nullptr;
+    uint32_t *d_off = (uint32_t *)(q + nb * (pairs ? 4 : 2));
+    void *ws = q + nb * (pairs ? 4 : 2) + ob;
+    hipStream_t s = dc->stream;
+    if (hipMemcpyAsync(d_kin + lo, kin + lo, m * 4, hipMemcpyHostToDevice, s) != hipSuccess) return RSORT_ERR_HIP;
+    if (pairs && hipMemcpyAsync(d_vin + lo, vin + lo, m * 4, hipMemcpyHostToDevice, s) != hipSuccess)
+        return RSORT_ERR_HIP;
+    if (hipMemcpyAsync(d_off, off, (size_t)(nseg + 1) * 4, hipMemcpyHostToDevice, s) != hipSuccess)
+        return RSORT_ERR_HIP;
+    st = seg_sort(d_kin, d_vin, d_kout, d_vout, n, d_off, nseg, ws, wsb, s);
+    if (st) {
+        (void)hipStreamSynchronize(s);
+        return st;
+    }
+    if (hipMemcpyAsync(kout + lo, d_kout + lo, m * 4, hipMemcpyDeviceToHost, s) != hipSuccess) return RSORT_ERR_HIP;
+    if (pairs && hipMemcpyAsync(vout + lo, d_vout + lo, m * 4, hipMemcpyDeviceToHost, s) != hipSuccess)
+        return RSORT_ERR_HIP;
+    uint32_t check = 0;
+    if (hipMemcpyAsync(&check, seg_carve(n, nseg, pairs, ws).counters + kSegCheckWord, 4, hipMemcpyDeviceToHost, s) !=
+        hipSuccess)
+        return RSORT_ERR_HIP;
+    if (hipStreamSynchronize(s) != hipSuccess) return RSORT_ERR_HIP;
+    return check ? RSORT_ERR_CHECK : RSORT_OK;
+}
+
 }  // namespace
 
 void rsort::profile_pause(int delta) { t_prof_paused += delta; }
@@ -713,6 +860,56 @@ int rsort_u32_pairs(const uint32_t *keys_in, const uint32_t *vals_in, uint32_t *
                     uint32_t *vals_out, int64_t n, int k_bits) {
     if (n > 0 && (!vals_in || !vals_out)) return RSORT_ERR_ARG;
     return host_sort(keys_in, vals_in, keys_out, vals_out, n, k_bits, nullptr);
+}
+
+int rsort_segmented_capacity(int pairs, int *small_keys, int *lds_keys) {
+    if (!small_keys || !lds_keys) return RSORT_ERR_ARG;
+    (void)pairs;  // (keys and pairs share both limits: the large shape's LDS holds 16384 keys and their values)
+    *small_keys = kSegSmallKeys;
+    *lds_keys = kSegLdsKeys;
+    return RSORT_OK;
+}
+
+size_t rsort_segmented_workspace_size(int64_t n, int64_t num_segments, int pairs) {
+    int st;
+    if (!seg_sizes_ok(n, num_segments, &st)) return 0;
+    return seg_carve(n, num_segments, pairs ? 1 : 0, nullptr).bytes;
+}
+
+int rsort_u32_segmented_device(const uint32_t *d_keys_in, const uint32_t *d_vals_in, uint32_t *d_keys_out,
+                               uint32_t *d_vals_out, int64_t n, const uint32_t *d_offsets, int64_t num_segments,
+                               void *d_workspace, size_t workspace_bytes, void *stream) {
+    return seg_sort(d_keys_in, d_vals_in, d_keys_out, d_vals_out, n, d_offsets, num_segments, d_workspace,
+                    workspace_bytes, (hipStream_t)stream);
+}
+
+int rsort_segmented_check(int64_t n, int64_t num_segments, int pairs, const void *d_workspace, int *flags,
+                          int64_t *class_counts, void *stream) {
+    int st;
+    if (!flags) return RSORT_ERR_ARG;
+    *flags = 0;
+    if (class_counts) memset(class_counts, 0, 4 * sizeof(int64_t));
+    if (!seg_sizes_ok(n, num_segments, &st)) return st;
+    if (n == 0 || num_segments == 0) return RSORT_OK;
+    if (!d_workspace) return RSORT_ERR_ARG;
+    const SegCarve c = seg_carve(n, num_segments, pairs ? 1 : 0, const_cast<void *>(d_workspace));
+    hipStream_t s = (hipStream_t)stream;
+    uint32_t h[kSegCheckWord + 1] = {0};
+    if (hipMemcpyAsync(h, c.counters, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess) return RSORT_ERR_HIP;
+    if (hipStreamSynchronize(s) != hipSuccess) return RSORT_ERR_HIP;
+    *flags = (int)(h[kSegCheckWord] & (kCheckRankOrder | kCheckOffsets));
+    if (class_counts) {  // (one wave or one small workgroup per segment: both are the small class)
+        class_counts[0] = (int64_t)h[kSegWave] + (int64_t)h[kSegSmall];
+        class_counts[1] = (int64_t)h[kSegLds];
+        class_counts[2] = (int64_t)h[kSegTiles];
+        class_counts[3] = (int64_t)h[kSegRejected];
+    }
+    return RSORT_OK;
+}
+
+int rsort_u32_segmented(const uint32_t *keys_in, const uint32_t *vals_in, uint32_t *keys_out, uint32_t *vals_out,
+                        int64_t n, const uint32_t *offsets, int64_t num_segments) {
+    return seg_host_sort(keys_in, vals_in, keys_out, vals_out, n, offsets, num_segments);
 }
 
 int rsort_pass_histogram(const rsort_plan *plan, const uint32_t *d_keys, int shift,

@@ -1,5 +1,5 @@
-// rsort_internal.hpp -- shared between the HIP kernels (rsort_kernels.hip) and the host
-// driver (rsort_capi.cpp). Not part of the public ABI (include/rsort.h is).
+// rsort_internal.hpp -- shared between the HIP kernels (rsort_kernels.hip, rsort_segmented.hip) and
+// the host driver (rsort_capi.cpp). Not part of the public ABI (include/rsort.h is).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -268,6 +268,52 @@ void profile_pause(int delta);
 // n (next-digit plans); kCheckRankOrder -- a lane-ordered scatter kernel's per-tile rank check failed.
 constexpr uint32_t kDoneErr = 1;
 constexpr uint32_t kCheckTable = 1u, kCheckRankOrder = 2u;
+
+// ------------------------------------------------------------------------------ segmented sort
+// (rsort_segmented.hip; rsort_u32_segmented_device.) Four kernels by segment length. Up to kSegWaveKeys keys ONE
+// WAVE sorts the segment (4 keys per lane, no workgroup barrier; 4 waves = 4 segments per 256-thread workgroup);
+// up to kSegSmallKeys keys a workgroup of 256 threads x 4 keys does (~8 KB of LDS for keys, ~12 KB for pairs:
+// 8 workgroups per CU either way); up to kSegLdsKeys keys one of 1024 threads x 16 keys (64 KB of tile, twice
+// that for pairs, + 16 KB of per-wave counter rows: one workgroup per CU); longer ones the multi-tile kernel.
+// The public classes (rsort_segmented_capacity, rsort_segmented_check) count the first two as "small".
+constexpr int kSegWaveKpt = 4;
+constexpr int kSegSmallThreads = 256, kSegSmallKpt = 4;
+constexpr int kSegLdsThreads = 1024, kSegLdsKpt = 16;
+constexpr int kSegWaveKeys = kWave * kSegWaveKpt;
+constexpr int kSegSmallKeys = kSegSmallThreads * kSegSmallKpt;
+constexpr int kSegLdsKeys = kSegLdsThreads * kSegLdsKpt;
+// Kernel kinds (launch_seg_sort) = list and counter indices; kSegRejected has a counter only.
+enum SegKind : int { kSegWave = 0, kSegSmall = 1, kSegLds = 2, kSegTiles = 3, kSegRejected = 4, kSegKinds = 4 };
+// The call's 256 B of counters and check words: [kind] segments of that kind (the lengths of the lists),
+// [kSegRejected] rejected ones, [kSegCheckWord] the check word -- kCheckRankOrder as in a sort's, kCheckOffsets
+// when a segment was rejected.
+constexpr uint32_t kSegCheckWord = 8;
+constexpr uint32_t kCheckOffsets = 4u;
+struct SegClassifyArgs {
+    const uint32_t *off;        // num_segments + 1 offsets
+    uint32_t *lists[kSegKinds]; // per kind: room for num_segments indices
+    uint32_t *counters;         // the 256 B above, cleared before the launch
+    uint64_t n;
+    uint32_t num_segments;
+};
+struct SegSortArgs {
+    const uint32_t *kin;
+    const uint32_t *vin;
+    uint32_t *kout;
+    uint32_t *vout;
+    uint32_t *ktmp;           // multi-tile kernel: the workspace ping-pong (n keys, n values)
+    uint32_t *vtmp;
+    const uint32_t *off;
+    const uint32_t *list;     // the class list and its length
+    const uint32_t *count;
+    uint32_t *check;          // the check word (lane-ordered kernels: kCheckRankOrder)
+    uint32_t rank_fault;      // rsort_inject_rank_fault
+};
+hipError_t launch_seg_classify(const SegClassifyArgs &a, hipStream_t s);
+// kind: SegKind; rank_algo: kRankAtomic or kRankCount; grid: workgroups (grid-stride over the list)
+hipError_t launch_seg_sort(int kind, int pairs, int rank_algo, const SegSortArgs &a, uint32_t grid, hipStream_t s);
+// Resident workgroups per CU of a segmented-sort kernel (occupancy query), 0 on error.
+int seg_blocks_per_cu(int kind, int pairs, int rank_algo);
 // Raw next-digit tables (every workgroup of a pass sums the whole R x C table for its own starts) cost
 // O(R x C) reads per workgroup, O(R x C^2) per pass: only plans of at most this many chunks (about one
 // resident wave: C2 has 1024) take them; larger ones keep the tail scan (DESIGN §8 measured

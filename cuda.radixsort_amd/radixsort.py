@@ -224,6 +224,13 @@ SIGNATURES = {
     "rsort_vendor_workspace_size": ([_i64], _sz),
     "rsort_u32_vendor_device": ([_vp, _vp, _i64, _vp, _sz, _vp], _int),
     "rsort_u32_vendor": ([_vp, _vp, _i64], _int),
+    "rsort_segmented_capacity": ([_int, ctypes.POINTER(_int), ctypes.POINTER(_int)], _int),
+    "rsort_segmented_workspace_size": ([_i64, _i64, _int], _sz),
+    "rsort_u32_segmented_device": ([_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _sz, _vp], _int),
+    "rsort_segmented_check": ([_i64, _i64, _int, _vp, ctypes.POINTER(_int), ctypes.POINTER(_i64), _vp], _int),
+    "rsort_u32_segmented": ([_vp, _vp, _vp, _vp, _i64, _vp, _i64], _int),
+    "rsort_vendor_segmented_workspace_size": ([_i64, _i64], _sz),
+    "rsort_u32_vendor_segmented_device": ([_vp, _vp, _i64, _vp, _i64, _vp, _sz, _vp], _int),
     "rsort_fingerprint_device": ([_vp, _vp, _i64, _vp, _vp], _int),
     "rsort_gen_uniform": ([_vp, _i64, ctypes.c_uint64, _vp], _int),
     "rsort_gen_zipf": ([_vp, _i64, ctypes.c_uint64, _vp, _i64, _vp], _int),
@@ -849,6 +856,107 @@ def vendor_sort_device(keys_in, keys_out, ws=None, stream=None):
         ws = workspace(need, keys_in.device)
     _check(_lib().rsort_u32_vendor_device(_ptr(keys_in), _ptr(keys_out), n, _ptr(ws), ws.numel(),
                                           _stream(stream)), "rsort_u32_vendor_device")
+
+
+# ---------------------------------------------------------------- segmented sort
+CHECK_OFFSETS = 4
+SEG_CLASSES = ("small", "lds", "tiles", "rejected")
+
+
+def segmented_capacity(pairs: bool = False) -> tuple[int, int]:
+    """rsort_segmented_capacity: (small, lds) LDS capacities in keys -- segments of up to `small` keys take
+    the 256-thread workgroups, up to `lds` the 1024-thread ones, longer ones the multi-tile path."""
+    a, b = ctypes.c_int(), ctypes.c_int()
+    _check(_lib().rsort_segmented_capacity(1 if pairs else 0, ctypes.byref(a), ctypes.byref(b)),
+           "rsort_segmented_capacity")
+    return int(a.value), int(b.value)
+
+
+def segmented_workspace_size(n: int, num_segments: int, pairs: bool = False) -> int:
+    return int(_lib().rsort_segmented_workspace_size(int(n), int(num_segments), 1 if pairs else 0))
+
+
+def _device_offsets(offsets, device):
+    """Offsets (int32 / int64 torch tensor, numpy array or list) -> device int32 tensor holding the u32 bits."""
+    _need_torch()
+    if isinstance(offsets, torch.Tensor):
+        if offsets.dtype == torch.int32:
+            return offsets.to(device).contiguous()
+        if offsets.dtype != torch.int64:
+            raise TypeError("offsets must be an int32 or int64 tensor")
+        o = offsets.to(device)
+        return torch.where(o >= (1 << 31), o - (1 << 32), o).to(torch.int32).contiguous()
+    a = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).astype(np.uint32))
+    return torch.from_numpy(a.view(np.int32)).to(device)
+
+
+def segmented_sort_device(keys_in, keys_out, offsets, vals_in=None, vals_out=None, ws=None, stream=None, n=None):
+    """rsort_u32_segmented_device: segment i = [offsets[i], offsets[i + 1]) of the first n keys (default: all
+    of keys_in) is sorted on its own, stable with values; stream-ordered. Returns (offsets on the device,
+    workspace) -- what segmented_check needs."""
+    n = keys_in.numel() if n is None else int(n)
+    off = _device_offsets(offsets, keys_in.device)
+    nseg = max(off.numel() - 1, 0)
+    pairs = vals_in is not None
+    need = segmented_workspace_size(n, nseg, pairs)
+    if ws is None:
+        ws = workspace(need, keys_in.device)
+    _check(_lib().rsort_u32_segmented_device(_ptr(keys_in), _ptr(vals_in), _ptr(keys_out), _ptr(vals_out), n,
+                                             _ptr(off), nseg, _ptr(ws), ws.numel(), _stream(stream)),
+           "rsort_u32_segmented_device")
+    return off, ws
+
+
+def segmented_check(n: int, num_segments: int, pairs: bool, ws, stream=None) -> tuple[int, dict]:
+    """rsort_segmented_check of the last segmented sort in `ws` (synchronises the stream): (flags -- CHECK_OFFSETS
+    / CHECK_RANK_ORDER bits, 0 = clean --, {"small", "lds", "tiles", "rejected"} segment counts)."""
+    f = ctypes.c_int()
+    cc = (ctypes.c_int64 * 4)()
+    _check(_lib().rsort_segmented_check(int(n), int(num_segments), 1 if pairs else 0, _ptr(ws), ctypes.byref(f), cc,
+                                        _stream(stream)), "rsort_segmented_check")
+    return int(f.value), {k: int(cc[i]) for i, k in enumerate(SEG_CLASSES)}
+
+
+def sortSegmentsByDevice(keys, offsets, out, vals=None, vals_out=None):
+    """rsort_u32_segmented over numpy host arrays: out[offsets[i]:offsets[i + 1]] = sorted segment i of keys
+    (vals_out: its values, stable); elements in no segment are left as they are. Synchronous."""
+    keys = _host_u32(keys, None, "keys")
+    n = keys.size
+    out = _host_u32(out, n, "out")
+    if (vals is None) != (vals_out is None):
+        raise ValueError("vals and vals_out go together")
+    if vals is not None:
+        vals = _host_u32(vals, n, "vals")
+        vals_out = _host_u32(vals_out, n, "vals_out")
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).astype(np.uint32))
+    nseg = max(off.size - 1, 0)
+    _check(_lib().rsort_u32_segmented(keys.ctypes.data, vals.ctypes.data if vals is not None else None,
+                                      out.ctypes.data, vals_out.ctypes.data if vals_out is not None else None,
+                                      int(n), off.ctypes.data, int(nseg)), "sortSegmentsByDevice")
+
+
+def sort_rows(keys_2d, out_2d, vals_2d=None, vals_out_2d=None, ws=None, stream=None):
+    """Every row of a contiguous 2-D tensor sorted on its own (the offsets are built on the device)."""
+    _need_torch()
+    for t in (keys_2d, out_2d, vals_2d, vals_out_2d):
+        if t is not None and (t.dim() != 2 or not t.is_contiguous() or t.shape != keys_2d.shape):
+            raise ValueError("sort_rows needs contiguous 2-D tensors of one shape")
+    rows, cols = keys_2d.shape
+    off = torch.arange(rows + 1, dtype=torch.int64, device=keys_2d.device) * cols
+    return segmented_sort_device(keys_2d, out_2d, off, vals_2d, vals_out_2d, ws=ws, stream=stream)
+
+
+def vendor_segmented_sort_device(keys_in, keys_out, offsets, ws=None, stream=None, n=None):
+    """rocPRIM's segmented radix sort over the same (valid) offsets: the comparator of segmented_sort_device."""
+    n = keys_in.numel() if n is None else int(n)
+    off = _device_offsets(offsets, keys_in.device)
+    nseg = max(off.numel() - 1, 0)
+    need = int(_lib().rsort_vendor_segmented_workspace_size(n, nseg))
+    if ws is None or ws.numel() < need:
+        ws = workspace(need, keys_in.device)
+    _check(_lib().rsort_u32_vendor_segmented_device(_ptr(keys_in), _ptr(keys_out), n, _ptr(off), nseg, _ptr(ws),
+                                                    ws.numel(), _stream(stream)), "rsort_u32_vendor_segmented_device")
+    return off, ws
 
 
 def fingerprint(keys, vals=None, stream=None) -> tuple[int, int]:

@@ -5,6 +5,8 @@
 # are built on the CPU side first (the command in each file's header); dev/README.md says which
 # DESIGN.md claim each lab backs.
 #
+#   seg [SHAPES]     the segmented sort against a loop of rsort_u32_device and rocPRIM's segmented sort, shapes
+#                    A..E of dev/seg_lab.py (default: all), one process per shape (dev/seg_out/seg.jsonl, and stdout)
 #   floors           round 6: production scatter passes with / without their stores (dev/floor_lab[_ns]), the C2
 #                    and pairs write-stream floors (dev/ceiling_lab c2 / pairs), the C2 / C4 bench lines
 #   round            pytest -m gpu (all) + the default bench line (what the driver runs at round end)
@@ -74,6 +76,16 @@ kt() {  # tag, bench args...
     stop_unless_ok $? "kt $tag"
 }
 case "$exp" in
+seg)
+    so=dev/seg_out
+    mkdir -p $so
+    : > $so/seg.jsonl
+    for s in ${@:-A B C D E}; do
+        timeout -k 10 240 python dev/seg_lab.py --shape "$s" >> $so/seg.jsonl 2>> $so/seg.err
+        stop_unless_ok $? "seg_lab $s"
+    done
+    cat $so/seg.jsonl
+    ;;
 floors)
     # one pass of each production scatter kernel with and without its output stores
     # (dev/floor_lab, dev/floor_lab_ns), the C2 and pairs write-stream floors (dev/ceiling_lab c2 / pairs)

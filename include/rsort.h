@@ -18,6 +18,7 @@
  *   rsort_pass_local_sort sortLocallyDataBlocks() alone                       Parallel7.cu:193-251
  *   rsort_u32_vendor     sortByThrust (the vendor comparator)                 Parallel7.cu:69-73
  *   (no counterpart)     rsort_u32_pairs*: key + u32 payload (BASELINE config 4)
+ *   (no counterpart)     rsort_u32_segmented*: many independent segments of one array in one call
  *   (no counterpart)     rsort_partition_device / rsort_bucket_starts: the multi-GPU
  *                        key-range partition step (BASELINE config 5)
  *
@@ -153,6 +154,65 @@ RSORT_API int rsort_u32_ex(const uint32_t *in, uint32_t *out, int64_t n, int k_b
                            int block_size, rsort_phase_times *times);
 RSORT_API int rsort_u32_pairs(const uint32_t *keys_in, const uint32_t *vals_in,
                               uint32_t *keys_out, uint32_t *vals_out, int64_t n, int k_bits);
+
+/* ---------------------------------------------------------------- segmented sort */
+/* Many independent segments of one array in one call (no reference counterpart; what a caller otherwise
+ * does with one rsort_u32_device call, a dozen launches, per segment).
+ *   - Segments: d_offsets holds num_segments + 1 u32 on the device; segment i is [off[i], off[i + 1]) of the
+ *     n keys. Segments that overlap each other are undefined.
+ *   - Output: segment i of the output is the ascending sort of segment i of the input, bit-exact with
+ *     Baseline1.cu's sortByHost applied to the segment; with values the sort is STABLE (Baseline1's loop
+ *     carrying the payload). There is no k_bits argument: the result does not depend on it, and the kernels
+ *     use 8-bit digits.
+ *   - Limits: 0 <= n < 2^32, 0 <= num_segments < 2^31; n == 0 or num_segments == 0 is a no-op that needs no
+ *     buffers; empty segments are allowed (they belong to no class below).
+ *   - Elements that lie in no segment (before off[0], after off[num_segments]) are not written.
+ *   - in == out is allowed for keys and for values; partial overlap is undefined; `in` is otherwise never
+ *     written.
+ *   - A segment with off[i] > off[i + 1] or off[i + 1] > n is REJECTED on the device before any access that
+ *     uses it: nothing is read or written for it, it is counted as rejected and RSORT_CHECK_OFFSETS is set in
+ *     the call's check word (rsort_segmented_check); all other segments are sorted normally.
+ *   - Stream-ordered on `stream`, no allocation, no host synchronisation, graph-capturable; the current
+ *     device; buffers (keys, values, offsets, workspace) may have any 4-byte alignment.
+ *   - Three classes by length, decided on the device (rsort_segmented_capacity gives the two limits, the same
+ *     for keys and pairs): up to *small_keys keys the segment is sorted inside LDS by one wave (up to 256 keys)
+ *     or one 256-thread workgroup, several per CU; up to *lds_keys by a 1024-thread workgroup; a longer
+ *     segment is sorted by ONE workgroup in four passes through the workspace. That multi-tile path is the correctness net, not a fast path -- one CU sorts the whole
+ *     segment -- so a caller with multi-million-key segments should sort each with rsort_u32_device.
+ *   - Ranking follows rsort_set_rank_algo as every sort does: lane-ordered returning LDS adds by default (where
+ *     rsort_lane_order_probe() == 1), with the rank check on every wave's first slot whenever it is full, in
+ *     every pass (RSORT_CHECK_RANK_ORDER in the check word; rsort_inject_rank_fault applies); the ballot peer
+ *     match otherwise (RSORT_RANK_BALLOT, RSORT_RANK_SPLIT, or a failed probe).
+ *   - Workspace bytes, with r(x) = x rounded up to a multiple of 256:
+ *         r(4 n) * (pairs ? 2 : 1)  the multi-tile path's ping-pong keys (and values)
+ *       + 4 * r(4 num_segments)     the lists of segment indices, one per kernel
+ *       + 256                       the class counters and check words
+ *   - Errors, returned before any HIP call: RSORT_ERR_SIZE (n), RSORT_ERR_ARG (num_segments out of range,
+ *     exactly one of the two value pointers, NULL keys / offsets / workspace), RSORT_ERR_ALIGN,
+ *     RSORT_ERR_WORKSPACE.
+ *   - rsort_profile_begin/end: the classification counts as RSORT_PHASE_HISTOGRAM, the sort kernels as
+ *     RSORT_PHASE_SCATTER. */
+/* LDS capacities of the segmented sort, in keys (multiples of 64): segments of up to *small_keys keys
+ * take the small workgroup shape, up to *lds_keys the large one; longer ones the multi-tile path. */
+RSORT_API int    rsort_segmented_capacity(int pairs, int *small_keys, int *lds_keys);
+RSORT_API size_t rsort_segmented_workspace_size(int64_t n, int64_t num_segments, int pairs);
+RSORT_API int    rsort_u32_segmented_device(const uint32_t *d_keys_in, const uint32_t *d_vals_in,
+                                            uint32_t *d_keys_out, uint32_t *d_vals_out, int64_t n,
+                                            const uint32_t *d_offsets, int64_t num_segments,
+                                            void *d_workspace, size_t workspace_bytes, void *stream);
+/* after the call has completed on `stream`: *flags = check bits (RSORT_CHECK_RANK_ORDER, RSORT_CHECK_OFFSETS);
+ * class_counts (may be NULL) receives {small, lds, multi-tile, rejected} segment counts. Synchronises the
+ * stream. Like the sort entry points above, the device entry cannot return these itself. */
+#define RSORT_CHECK_OFFSETS 4
+RSORT_API int    rsort_segmented_check(int64_t n, int64_t num_segments, int pairs, const void *d_workspace,
+                                       int *flags, int64_t *class_counts, void *stream);
+/* host -> host, synchronous, library-owned cached workspace (as rsort_u32). The offsets are checked on the
+ * host first (RSORT_ERR_ARG for a decreasing pair or one beyond n, before the device is touched); only the
+ * covered range [off[0], off[num_segments]) is copied in and out. RSORT_ERR_NODEV without a device (there is
+ * no CPU fallback); RSORT_ERR_CHECK when the rank check failed. */
+RSORT_API int    rsort_u32_segmented(const uint32_t *keys_in, const uint32_t *vals_in, uint32_t *keys_out,
+                                     uint32_t *vals_out, int64_t n, const uint32_t *offsets,
+                                     int64_t num_segments);
 
 /* ---------------------------------------------------------------- one digit pass, device */
 /* digit(key) = (key >> shift) & (bins - 1). Table layout: d_table[digit * num_chunks + chunk]. */
@@ -522,6 +582,12 @@ RSORT_API size_t rsort_vendor_workspace_size(int64_t n);
 RSORT_API int rsort_u32_vendor_device(const uint32_t *d_in, uint32_t *d_out, int64_t n,
                                       void *d_workspace, size_t workspace_bytes, void *stream);
 RSORT_API int rsort_u32_vendor(const uint32_t *in, uint32_t *out, int64_t n);
+/* rocPRIM's segmented radix sort over the same offsets as rsort_u32_segmented_device (keys only; the
+ * offsets must be valid: rocPRIM does not check them). A comparator only. */
+RSORT_API size_t rsort_vendor_segmented_workspace_size(int64_t n, int64_t num_segments);
+RSORT_API int rsort_u32_vendor_segmented_device(const uint32_t *d_in, uint32_t *d_out, int64_t n,
+                                                const uint32_t *d_offsets, int64_t num_segments,
+                                                void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------- output check */
 /* d_out[0] = sum over i of fmix64(d_vals[i] << 32 | d_keys[i]) mod 2^64 (d_vals may be NULL: 0),
