@@ -12,6 +12,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <math.h>
+
 #include <algorithm>
 #include <atomic>
 #include <mutex>
@@ -29,6 +31,14 @@ std::atomic<int> g_rank_algo{RSORT_RANK_MATCH};
 std::atomic<int> g_group_chunks{1};
 std::atomic<int> g_table_fault{0};  // rsort_inject_table_fault (tests)
 std::atomic<int> g_rank_fault{0};   // rsort_inject_rank_fault (tests)
+std::atomic<int> g_hybrid{RSORT_HYBRID_AUTO};  // rsort_set_hybrid
+
+// Hybrid-eligible sorts enqueue both kernel sequences; every launch carries the device-side mode word and the
+// value it works under (HistArgs::mode). {nullptr, 0}: no test.
+struct Gate {
+    const uint32_t *mode = nullptr;
+    uint32_t want = 0;
+};
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -37,6 +47,7 @@ struct ProfRec {
     int phase;
     int64_t keys;
     hipEvent_t a, b;
+    Gate gate;  // a launch of a hybrid-eligible sort: counted only if its route ran (rsort_profile_end)
 };
 
 struct Profiler {
@@ -64,12 +75,13 @@ struct PhaseScope {
     bool active = false;
     ProfRec rec{};
     hipStream_t s;
-    PhaseScope(int phase, int64_t keys, hipStream_t stream) : s(stream) {
+    PhaseScope(int phase, int64_t keys, hipStream_t stream, Gate gate = Gate{}) : s(stream) {
         if (t_prof_paused > 0) return;
         std::lock_guard<std::mutex> g(g_prof.mu);
         if (!g_prof.on) return;
         rec.phase = phase;
         rec.keys = keys;
+        rec.gate = gate;
         rec.a = g_prof.get();
         rec.b = g_prof.get();
         if (!rec.a || !rec.b) return;
@@ -301,8 +313,12 @@ Carve carve(const rsort_plan &p, void *ws) {
 // adds runs of equal pairs once (rs_histogram's run path), so pass 3 gets its own cut plan too.
 int do_histogram_joint(const rsort_plan &p, const uint32_t *keys, int shift, uint32_t *table,
                        uint32_t *joint, const uint32_t *enable, hipStream_t s, bool zero_joint,
-                       uint32_t *rows, uint32_t *rows_cnt, uint32_t *done = nullptr) {
+                       uint32_t *rows, uint32_t *rows_cnt, uint32_t *done = nullptr, int shift2 = 0,
+                       Gate gate = Gate{}) {
     HistArgs a{};
+    a.shift2 = (uint32_t)shift2;
+    a.mode = gate.mode;
+    a.mode_want = gate.want;
     a.done = done;
     a.rows = rows;
     a.rows_cnt = rows_cnt;
@@ -316,7 +332,7 @@ int do_histogram_joint(const rsort_plan &p, const uint32_t *keys, int shift, uin
     a.split = 1;
     a.joint = joint;
     a.joint_enable = enable;
-    PhaseScope ps(RSORT_PHASE_HISTOGRAM, p.n, s);
+    PhaseScope ps(RSORT_PHASE_HISTOGRAM, p.n, s, gate);
     // the first joint count of a sort clears the counts; a later one finds them cleared by the
     // copy-mode histogram that used them (or, where that pass fell back, is disabled by `enable`)
     // (the rows counter sits after the joint counts: cleared with them)
@@ -331,8 +347,8 @@ int do_histogram_joint(const rsort_plan &p, const uint32_t *keys, int shift, uin
 // (ctab: a cut plan's pieces become row tasks where every chunk wrote its rows).
 int do_joint_bounds(const rsort_plan &p, const uint32_t *joint, const uint32_t *enable, uint32_t *bounds,
                     uint32_t *plan, uint32_t *pcounts, const uint32_t *ctab, uint32_t *rows_cnt,
-                    const uint32_t *rowone, hipStream_t s) {
-    PhaseScope ps(RSORT_PHASE_HISTOGRAM, p.n, s);
+                    const uint32_t *rowone, hipStream_t s, Gate gate = Gate{}) {
+    PhaseScope ps(RSORT_PHASE_HISTOGRAM, p.n, s, gate);
     // a group may take one tile more than a fixed chunk; a cut-plan chunk boundary moves to a
     // group boundary up to half a tile (and a quarter chunk) away
     const uint32_t snap = (uint32_t)std::min<int64_t>(p.tile_keys / 2, p.n / (4 * (int64_t)kJointBins));
@@ -341,15 +357,17 @@ int do_joint_bounds(const rsort_plan &p, const uint32_t *joint, const uint32_t *
     const uint32_t weighted = (enable == nullptr && cut_weights()) ? 1u : 0u;
     return hip_status(launch_joint_bounds(joint, enable, bounds, plan, pcounts, (uint64_t)p.n,
                                           (uint64_t)p.chunk_keys + (uint64_t)p.tile_keys, snap, weighted, s,
-                                          ctab, rows_cnt, rowone));
+                                          ctab, rows_cnt, rowone, gate.mode, gate.want));
 }
 
 int do_histogram(const rsort_plan &p, const uint32_t *keys, int shift, uint32_t *table,
                  int dmode, const uint32_t *split, int nsplit, hipStream_t s,
                  const uint32_t *bounds = nullptr, uint32_t *copy_src = nullptr,
                  const uint32_t *plan = nullptr, uint32_t *pcounts = nullptr, uint32_t *zero = nullptr,
-                 uint32_t *done = nullptr, uint32_t *rows = nullptr) {
+                 uint32_t *done = nullptr, uint32_t *rows = nullptr, Gate gate = Gate{}) {
     HistArgs a{};
+    a.mode = gate.mode;
+    a.mode_want = gate.want;
     a.rows = rows;
     a.zero = zero;
     a.zero_n = zero ? (uint64_t)p.table_entries : 0u;
@@ -380,14 +398,17 @@ int do_histogram(const rsort_plan &p, const uint32_t *keys, int shift, uint32_t 
     } else if (p.num_chunks < want && p.chunk_keys >= 8 * 4096) {
         a.split = (uint32_t)std::min<int64_t>({(want + p.num_chunks - 1) / p.num_chunks, p.chunk_keys / 4096, 64});
     }
-    PhaseScope ps(RSORT_PHASE_HISTOGRAM, p.n, s);
+    PhaseScope ps(RSORT_PHASE_HISTOGRAM, p.n, s, gate);
     if (a.split > 1 && hipMemsetAsync(table, 0, (size_t)p.table_entries * 4, s) != hipSuccess) return RSORT_ERR_HIP;
     return hip_status(launch_histogram(p.k_bits, dmode, a, s));
 }
 
 int do_scan(const rsort_plan &p, uint32_t *table, uint32_t *bsums, hipStream_t s, uint32_t *zero = nullptr,
-            uint32_t *done = nullptr, const Carve *cut = nullptr, const uint32_t *group_flag = nullptr) {
+            uint32_t *done = nullptr, const Carve *cut = nullptr, const uint32_t *group_flag = nullptr,
+            Gate gate = Gate{}) {
     ScanArgs a{};
+    a.mode = gate.mode;
+    a.mode_want = gate.want;
     a.done = done;
     if (cut != nullptr) {
         // a digit-group pass: under a cut plan the scan assembles the table first
@@ -402,7 +423,7 @@ int do_scan(const rsort_plan &p, uint32_t *table, uint32_t *bsums, hipStream_t s
     a.zero_n = zero ? (uint64_t)p.table_entries : 0u;
     a.m = (uint64_t)p.table_entries;
     a.nblocks = (uint32_t)p.scan_blocks;
-    PhaseScope ps(RSORT_PHASE_SCAN, p.table_entries, s);
+    PhaseScope ps(RSORT_PHASE_SCAN, p.table_entries, s, gate);
     return hip_status(launch_scan(a, s));
 }
 
@@ -411,8 +432,10 @@ int do_scatter(const rsort_plan &p, const uint32_t *kin, const uint32_t *vin, ui
                const uint32_t *split, int nsplit, hipStream_t s, const uint32_t *bounds = nullptr,
                uint32_t *next_table = nullptr, uint32_t *tail_zero = nullptr, uint32_t *done = nullptr,
                const uint32_t *cl_select = nullptr, int raw_table = 0, uint32_t *zero_table = nullptr,
-               uint32_t *check = nullptr) {
+               uint32_t *check = nullptr, Gate gate = Gate{}) {
     ScatterArgs a{};
+    a.mode = gate.mode;
+    a.mode_want = gate.want;
     a.check = check;
     a.rank_fault = g_rank_fault.load() ? 1u : 0u;
     a.raw_table = raw_table ? 1u : 0u;
@@ -441,7 +464,7 @@ int do_scatter(const rsort_plan &p, const uint32_t *kin, const uint32_t *vin, ui
     if ((bounds || next_table || raw_table) && !(rank == kRankAtomic && aligned16 && !local_only && dmode == kDigitShift))
         return RSORT_ERR_ARG;  // group chunks, next-digit counts, raw tables: rs_scatter_lines only
     // a multi-GPU partition's scatter (splitter digits) is recorded apart from the sort's passes
-    PhaseScope ps(dmode == kDigitSplit ? RSORT_PHASE_PARTITION : RSORT_PHASE_SCATTER, p.n, s);
+    PhaseScope ps(dmode == kDigitSplit ? RSORT_PHASE_PARTITION : RSORT_PHASE_SCATTER, p.n, s, gate);
     return hip_status(launch_scatter(p.k_bits, p.pairs, rank, dmode, geom, local_only ? 0 : aligned16, a, s));
 }
 
@@ -458,8 +481,65 @@ int check_plan(const rsort_plan *p) {
     return RSORT_OK;
 }
 
+// ------------------------------------------------------------------------------ hybrid route
+// (rsort_hybrid.hip.) The automatic n range: from kHybMinKeys (measured: DESIGN §3, profiles/hybrid_ab.json;
+// RSORT_HYB_MIN_KEYS under RSORT_LAB=1 for A/B runs) up to where the MEAN bucket n / 65536 reaches the capacity.
+// The bucket phase pays ~4.7 us per bucket whatever its size (65536 buckets whatever n), so the route loses
+// at 2^29 keys (4.50 against 4.17 ms) and 2^28 (3.13 against 2.25) and wins from about 0.7 x 2^30 keys on:
+// 3 x 2^28 keys 5.96 against 6.17 ms (-3.5 %), 7 x 2^27 keys 6.76 against 7.19 (-6 %).
+constexpr int64_t kHybMinKeys = (int64_t)3 << 28;
+constexpr int64_t kHybMaxKeys = (int64_t)kHybCapacity * kHybBuckets;
+int64_t hyb_min_keys() {
+    static const int64_t v = [] {
+        const char *e = lab_env("RSORT_HYB_MIN_KEYS");
+        const long long x = e ? atoll(e) : 0;
+        return (x >= 1 && x < ((long long)1 << 32)) ? (int64_t)x : kHybMinKeys;
+    }();
+    return v;
+}
+
+// Bucket-kernel workgroups per resident slot (grid-stride over the buckets): 2^30 uniform keys sorted in 7.733 ms
+// with 1, 7.680 with 2, 7.672 with 4 (same-box bench runs; a workgroup that ends early leaves its slot to a fresh
+// one instead of the slowest deciding).
+constexpr int kHybGridMult = 4;
+
+// The sample gate's threshold. Each of the gate's kHybGateGroups workgroups reads m = min(n, kHybSample) /
+// kHybGateGroups keys at a fixed stride over its part of the input and counts them by their top 16 bits. A bucket
+// the hybrid can still hold has at most kHybCapacity of the n keys, so its count in one workgroup is (for keys
+// whose value does not depend on their position) at most Poisson with lambda = m * capacity / n: 0.0176 at 2^30
+// keys, 0.0234 at 3 x 2^28. The threshold is the smallest T with 65536 buckets x 64 workgroups x
+// P(Poisson(lambda) >= T) < 1e-9 -- no acceptable input, uniform keys (lambda = m / 65536) least of all, reaches
+// it in a billion sorts: T = 7 of 1024 keys at 2^30. A bucket that does reach it holds ~0.7 % of a 64th of the
+// input, hundreds of times the capacity's share: Zipf and hot keys (shares of 7 % and 25 %), all-equal and
+// small-integer keys (every key in one bucket). Inputs skewed less than that -- and inputs whose parts are each
+// clustered in a few buckets the gate may call skewed although the whole is balanced: they take the LSD passes --
+// pass the gate and are decided by the exact count, for one extra histogram read.
+// (tail bound: P(X >= k) <= pmf(k) / (1 - lambda / (k + 1)) for k + 1 > lambda)
+uint32_t gate_threshold(int64_t n) {
+    const double m = (double)std::min<int64_t>(n, kHybSample) / (double)kHybGateGroups;
+    const double lam = m * std::max(1.0 / (double)kHybBuckets, (double)kHybCapacity / (double)std::max<int64_t>(n, 1));
+    double lp = -lam;  // log pmf(0)
+    for (uint32_t k = 0; k < 65535u; ++k) {
+        if ((double)(k + 1) > lam) {
+            const double tail = exp(lp) / (1.0 - lam / (double)(k + 1));
+            if (tail * (double)kHybBuckets * (double)kHybGateGroups < 1e-9) return std::max(k, 2u);
+        }
+        lp += log(lam) - log((double)(k + 1));
+    }
+    return 65535u;
+}
+
+// Whether a sort takes the hybrid route's launches (the device still decides): keys only, k = 8, a joint plan on
+// the digit-group path (lane-ordered ranks, both outputs line-capable: `joint`), in != out, n in the range.
+bool hybrid_eligible(const rsort_plan &p, bool joint, bool inplace, bool allow) {
+    const int hm = g_hybrid.load();
+    if (!allow || hm == RSORT_HYBRID_OFF || !joint || p.pairs || inplace || p.passes != 4) return false;
+    if (hm == RSORT_HYBRID_FORCE) return true;
+    return p.n >= hyb_min_keys() && p.n <= kHybMaxKeys;
+}
+
 int sort_planned(const rsort_plan &p, const uint32_t *kin, const uint32_t *vin, uint32_t *kout,
-                 uint32_t *vout, void *ws, size_t wsb, hipStream_t s) {
+                 uint32_t *vout, void *ws, size_t wsb, hipStream_t s, bool allow_hybrid = true) {
     int st = check_plan(&p);
     if (st) return st;
     if (p.n == 0) return RSORT_OK;
@@ -500,6 +580,61 @@ int sort_planned(const rsort_plan &p, const uint32_t *kin, const uint32_t *vin, 
     const bool rawt = nextc && !nx_tail() && p.num_chunks <= kRawTableMaxChunks;
     uint32_t *const rot[3] = {c.table, c.table2, c.table3};
     uint32_t *const rows = piece_rows() ? c.rows : nullptr, *const rows_cnt = rows ? c.rows_cnt : nullptr;
+    // Hybrid route: gate, joint count of (digit 3, digit 2), mode + bucket starts, pass A in -> out, pass B
+    // out -> tmp, bucket phase tmp -> out; then the LSD passes below, which run when the mode word says so.
+    // Every kernel of the unselected route leaves at once.
+    const bool hyb = hybrid_eligible(p, joint, inplace || kin == c.tmp_k, allow_hybrid);
+    Gate lsd{};
+    if (hyb) {
+        const uint32_t *mode = c.done + kHybMode;
+        const bool force = g_hybrid.load() == RSORT_HYBRID_FORCE;
+        // the joint count runs when the gate's flag stayed 0 (FORCE: always)
+        const Gate g_try = force ? Gate{} : Gate{c.joint + kHybGateFlag, 0u}, g_run{mode, kHybRun};
+        lsd = Gate{mode, kHybLsd};
+        uint32_t *hb = c.plan;  // pass B's chunks (the cut-plan area: the LSD passes use it only when they run)
+        HybArgs h{};
+        h.kin = kin;
+        h.kout = kout;
+        h.joint = c.joint;
+        h.bounds = hb;
+        h.gflags = c.bounds;
+        h.done = c.done;
+        h.n = (uint64_t)p.n;
+        h.threshold = gate_threshold(p.n);
+        h.force = force ? 1u : 0u;
+        h.rank_fault = g_rank_fault.load() ? 1u : 0u;
+        hyb_note_bucket();
+        {
+            // the one clear of the joint counts, with the rows counter and the gate's flag behind them: the LSD
+            // passes find them cleared -- never counted after a skewed verdict, cleared again by rs_hyb_bounds
+            // after an overflow
+            PhaseScope ps(RSORT_PHASE_HISTOGRAM, std::min<int64_t>(p.n, kHybSample), s);
+            if (hipMemsetAsync(c.joint, 0, (size_t)kJointBins * kJointBins * 4 + 16, s) != hipSuccess) return RSORT_ERR_HIP;
+            if ((st = hip_status(launch_hyb_gate(h, s)))) return st;
+        }
+        if ((st = do_histogram_joint(p, kin, 24, c.table, c.joint, nullptr, s, false, nullptr, nullptr, nullptr, 16,
+                                     g_try)))
+            return st;
+        {
+            PhaseScope ps(RSORT_PHASE_HISTOGRAM, p.n, s);
+            if ((st = hip_status(launch_hyb_bounds(h, s)))) return st;
+        }
+        if ((st = do_scan(p, c.table, c.bsums, s, nullptr, nullptr, nullptr, nullptr, g_run))) return st;
+        if ((st = do_scatter(p, kin, nullptr, kout, nullptr, 24, c.table, 0, kDigitShift, nullptr, 0, s, nullptr,
+                             nullptr, nullptr, nullptr, nullptr, 0, nullptr, c.done + kDoneErr, g_run)))
+            return st;
+        if ((st = do_scatter(p, kout, nullptr, c.tmp_k, nullptr, 16, c.joint, 0, kDigitShift, nullptr, 0, s, hb,
+                             nullptr, nullptr, nullptr, nullptr, 0, nullptr, c.done + kDoneErr, g_run)))
+            return st;
+        {
+            const int cus = std::max(1, device_cus());
+            const int bpc = std::max(1, hyb_blocks_per_cu());
+            const uint32_t grid = (uint32_t)std::min<int64_t>(kHybBuckets, (int64_t)cus * bpc * kHybGridMult);
+            h.kin = c.tmp_k;
+            PhaseScope ps(RSORT_PHASE_SCATTER, p.n, s, g_run);
+            if ((st = hip_status(launch_hyb_bucket(h, grid, s)))) return st;
+        }
+    }
     for (int i = 0; i < P; ++i) {
         const int shift = i * p.k_bits;
         const bool to_out = ((P - 1 - i) % 2) == 0;  // the last pass always lands in `out`
@@ -516,24 +651,25 @@ int sort_planned(const rsort_plan &p, const uint32_t *kin, const uint32_t *vin, 
         const uint32_t *enable = (count_joint && i >= 2) ? c.bounds + (i / 2 - 1) * kBoundsWords : nullptr;
         // pass 0's histogram clears the check words (rsort_plan_check: a clean record for this sort)
         if (count_joint) {
-            if ((st = do_histogram_joint(p, sk, shift, c.table, c.joint, enable, s, i == 0, rows, rows_cnt,
-                                         i == 0 ? c.done : nullptr)))
+            // (a hybrid-eligible sort: the gate cleared the check words, the hybrid launches the joint counts)
+            if ((st = do_histogram_joint(p, sk, shift, c.table, c.joint, enable, s, i == 0 && !hyb, rows, rows_cnt,
+                                         (i == 0 && !hyb) ? c.done : nullptr, 0, lsd)))
                 return st;
         } else if (!(nextc && i > 0) &&
                    (st = do_histogram(p, sk, shift, tab, kDigitShift, nullptr, 0, s, bounds, c.joint, c.plan,
                                       c.pcounts, rawt ? nxt : nullptr, i == 0 ? c.done : nullptr,
-                                      bounds ? rows : nullptr))) {
+                                      bounds ? rows : nullptr, lsd))) {
             return st;
         }
         // next-digit plans: pass 0's table is scanned by launches (which also arm the tail counter;
         // raw tables: no scan at all, the histogram cleared the next table), every later table by the
         // previous scatter's last workgroup (raw tables: by every workgroup of the pass itself)
         if (!(nextc && i > 0) && !rawt &&
-            (st = do_scan(p, tab, c.bsums, s, nxt, nextc ? c.done : nullptr, bounds ? &c : nullptr, bounds)))
+            (st = do_scan(p, tab, c.bsums, s, nxt, nextc ? c.done : nullptr, bounds ? &c : nullptr, bounds, lsd)))
             return st;
         // the next pass's chunks (after the scan: a cut plan finds the previous chunks' positions in it)
         if (count_joint && (st = do_joint_bounds(p, c.joint, enable, c.bounds + (i / 2) * kBoundsWords, c.plan,
-                                                 c.pcounts, tab, rows_cnt, rows ? rows + kRowsWords : nullptr, s)))
+                                                 c.pcounts, tab, rows_cnt, rows ? rows + kRowsWords : nullptr, s, lsd)))
             return st;
         // passes after the first of a digit-group sort: where the previous odd pass's groups were
         // unbalanced (skewed, duplicate-heavy keys: runs of equal keys in this pass's input), the
@@ -541,7 +677,7 @@ int sort_planned(const rsort_plan &p, const uint32_t *kin, const uint32_t *vin, 
         const uint32_t *cl = (joint && i >= 1) ? c.bounds + ((i - 1) / 2) * kBoundsWords : nullptr;
         if ((st = do_scatter(p, sk, sv, dk, dv, shift, tab, 0, kDigitShift, nullptr, 0, s, bounds, nxt,
                              (nxt && !rawt) ? tab : nullptr, (nextc && (nxt || rawt)) ? c.done : nullptr, cl,
-                             rawt, clr, c.done + kDoneErr)))
+                             rawt, clr, c.done + kDoneErr, lsd)))
             return st;
         // test hook: corrupt the raw table pass 1 reads (its total is then not n: every pass-1 workgroup
         // writes nothing and records the failure for rsort_plan_check / RSORT_ERR_CHECK)
@@ -827,6 +963,14 @@ int rsort_sort_planned(const rsort_plan *plan, const uint32_t *d_keys_in, const 
                         workspace_bytes, (hipStream_t)stream);
 }
 
+int rsort_sort_planned_ex(const rsort_plan *plan, const uint32_t *d_keys_in, const uint32_t *d_vals_in,
+                          uint32_t *d_keys_out, uint32_t *d_vals_out, void *d_workspace,
+                          size_t workspace_bytes, void *stream, int flags) {
+    if (!plan || (flags & ~RSORT_SORT_NO_HYBRID)) return RSORT_ERR_ARG;
+    return sort_planned(*plan, d_keys_in, d_vals_in, d_keys_out, d_vals_out, d_workspace,
+                        workspace_bytes, (hipStream_t)stream, !(flags & RSORT_SORT_NO_HYBRID));
+}
+
 int rsort_u32_device(const uint32_t *d_in, uint32_t *d_out, int64_t n, int k_bits,
                      void *d_workspace, size_t workspace_bytes, void *stream) {
     rsort_plan p;
@@ -973,6 +1117,46 @@ int rsort_set_group_chunks(int enable) {
 
 int rsort_get_group_chunks(void) { return g_group_chunks.load(); }
 
+int rsort_set_hybrid(int mode) {
+    if (mode != RSORT_HYBRID_AUTO && mode != RSORT_HYBRID_OFF && mode != RSORT_HYBRID_FORCE) return RSORT_ERR_ARG;
+    g_hybrid.store(mode);
+    return RSORT_OK;
+}
+
+int rsort_get_hybrid(void) { return g_hybrid.load(); }
+
+int rsort_hybrid_capacity(void) { return (int)kHybCapacity; }
+
+int rsort_hybrid_range(int64_t *min_keys, int64_t *max_keys) {
+    if (!min_keys || !max_keys) return RSORT_ERR_ARG;
+    *min_keys = hyb_min_keys();
+    *max_keys = kHybMaxKeys;
+    return RSORT_OK;
+}
+
+int rsort_hybrid_gate_threshold(int64_t n) {
+    if (n <= 0 || n >= ((int64_t)1 << 32)) return -RSORT_ERR_SIZE;
+    return (int)gate_threshold(n);
+}
+
+int rsort_hybrid_report(const rsort_plan *plan, const void *d_workspace, int *report, void *stream) {
+    if (!plan || !report || !d_workspace) return RSORT_ERR_ARG;
+    int st = check_plan(plan);
+    if (st) return st;
+    for (int i = 0; i < 4; ++i) report[i] = 0;
+    if (plan->n == 0) return RSORT_OK;
+    const Carve c = carve(*plan, const_cast<void *>(d_workspace));
+    hipStream_t s = (hipStream_t)stream;
+    uint32_t h[4] = {0, 0, 0, 0};
+    if (hipMemcpyAsync(h, c.done + kHybMode, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess) return RSORT_ERR_HIP;
+    if (hipStreamSynchronize(s) != hipSuccess) return RSORT_ERR_HIP;
+    report[0] = (int)h[kHybEligible - kHybMode];
+    report[1] = (int)h[kHybGate - kHybMode];  // RSORT_GATE_*
+    report[2] = (int)h[kHybMax - kHybMode];
+    report[3] = h[0] == kHybRun ? 1 : 0;
+    return RSORT_OK;
+}
+
 int rsort_group_flags(const rsort_plan *plan, const void *d_workspace, int *flags, void *stream) {
     if (!plan || !flags || !d_workspace) return RSORT_ERR_ARG;
     int st = check_plan(plan);
@@ -1075,10 +1259,27 @@ int rsort_profile_end(rsort_phase_times *out) {
     rsort_phase_times t;
     memset(&t, 0, sizeof(t));
     int st = RSORT_OK;
+    // launches of hybrid-eligible sorts carry their route (Gate): those of the route that did not run left at once
+    // and are not counted. The mode word is read here, after the events: it is the LAST sort's in that workspace
+    // (a profile over sorts of different inputs in one workspace counts them all by the last one's route).
+    std::vector<std::pair<const uint32_t *, uint32_t>> modes;
+    auto mode_of = [&](const uint32_t *m) {
+        for (auto &kv : modes)
+            if (kv.first == m) return kv.second;
+        uint32_t v = 0xFFFFFFFFu;
+        if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&v, m, 4, hipMemcpyDeviceToHost) != hipSuccess)
+            v = 0xFFFFFFFFu;  // (unreadable, e.g. a freed workspace: count every launch)
+        modes.emplace_back(m, v);
+        return v;
+    };
     for (auto &r : recs) {
         if (hipEventSynchronize(r.b) != hipSuccess) {
             st = RSORT_ERR_HIP;
             continue;
+        }
+        if (r.gate.mode != nullptr) {
+            const uint32_t v = mode_of(r.gate.mode);
+            if (v != 0xFFFFFFFFu && v != r.gate.want) continue;
         }
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, r.a, r.b) != hipSuccess) {

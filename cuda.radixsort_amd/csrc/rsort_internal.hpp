@@ -96,6 +96,13 @@ struct HistArgs {
     // Piece-mode launches: the rows the plan's row tasks sum.
     uint32_t *rows;
     uint32_t *rows_cnt;
+    // joint-count histograms: the second digit's shift when it is not shift + kJointBits (0: that default).
+    // The hybrid route counts (digit 3, digit 2): shift = 24, shift2 = 16.
+    uint32_t shift2;
+    // hybrid-eligible sorts (rsort_hybrid.hip): != nullptr -> the kernel works only when *mode == mode_want
+    // and leaves at once otherwise (both kernel sequences are enqueued, the device picks one)
+    const uint32_t *mode;
+    uint32_t mode_want;
 };
 
 struct ScatterArgs {
@@ -144,6 +151,9 @@ struct ScatterArgs {
     // kCheckRankOrder; rank_fault != 0: the test hook that swaps two ranks per digit in every checked slot
     uint32_t *check;
     uint32_t rank_fault;
+    // hybrid-eligible sorts: as HistArgs::mode (whole-line kernels only)
+    const uint32_t *mode;
+    uint32_t mode_want;
 };
 
 struct ScanArgs {
@@ -160,6 +170,9 @@ struct ScanArgs {
     uint32_t *joint;
     const uint32_t *plan;
     const uint32_t *pcounts;
+    // hybrid-eligible sorts: as HistArgs::mode
+    const uint32_t *mode;
+    uint32_t mode_want;
 };
 
 // Launchers (rsort_kernels.hip). All return hipSuccess or the launch error.
@@ -230,7 +243,8 @@ hipError_t launch_joint_bounds(const uint32_t *joint, const uint32_t *enable, ui
                                uint32_t *plan, uint32_t *pcounts, uint64_t n, uint64_t max_keys,
                                uint32_t snap, uint32_t weighted, hipStream_t s,
                                const uint32_t *ctab = nullptr, uint32_t *rows_cnt = nullptr,
-                               const uint32_t *rowone = nullptr);
+                               const uint32_t *rowone = nullptr, const uint32_t *mode = nullptr,
+                               uint32_t mode_want = 0);
 // rank_algo: internal RankAlgo. aligned16: the whole-line kernels may run -- keys-only: always
 // (any 4-B-aligned kout; launch_scatter shifts positions to kout's 128-B-aligned base); pairs: when
 // (vout - kout) % 16 == 0 (otherwise the same plan runs rs_scatter with the same tiles).
@@ -259,6 +273,9 @@ int scatter_blocks_per_cu(int bits, int pairs, int rank_algo, int geom, int dmod
 // Names of the scatter kernel instantiations launched since the last reset, ';'-joined into buf
 // (truncated to len - 1 characters); returns the full length. reset != 0 clears the record.
 size_t scatter_kernels_used(char *buf, size_t len, int reset);
+// A kernel of another translation unit (the hybrid route's bucket kernel) for that record: registered by name
+// on first use and noted as launched.
+void note_kernel_used(const void *fn, const char *name);
 // rsort_profile_*: while a thread's pause count is > 0 its launches record no phase events (the
 // multi-GPU sort's sample sort, which is part of its plan phase, not of the measured passes)
 void profile_pause(int delta);
@@ -268,6 +285,50 @@ void profile_pause(int delta);
 // n (next-digit plans); kCheckRankOrder -- a lane-ordered scatter kernel's per-tile rank check failed.
 constexpr uint32_t kDoneErr = 1;
 constexpr uint32_t kCheckTable = 1u, kCheckRankOrder = 2u;
+
+// ------------------------------------------------------------------------------ hybrid route
+// (rsort_hybrid.hip; sort_planned in rsort_capi.cpp.) Keys-only k = 8 sorts of ~2^29..2^30 keys whose top 16
+// bits spread evenly: two MSD passes by digits 3 and 2 (the line scatter kernel) leave 65536 contiguous buckets,
+// and one kernel sorts each bucket by its low 16 bits inside LDS -- three 8-B/key passes instead of four.
+// The route is picked on the device: done[kHybMode] is the mode word every kernel of both sequences tests
+// (HistArgs::mode), done[kHybGate .. kHybEligible] the report rsort_hybrid_report reads. Pass 0's histogram
+// clears the four words with the check words (an ineligible sort: all 0); an eligible sort's exact-count kernel
+// (rs_hyb_bounds) writes them.
+constexpr uint32_t kHybMode = 4, kHybGate = 5, kHybMax = 6, kHybEligible = 7;
+constexpr uint32_t kHybLsd = 0, kHybRun = 2;                       // done[kHybMode]
+constexpr uint32_t kGateNone = 0, kGatePass = 1, kGateSkewed = 2;  // done[kHybGate]
+constexpr int kHybThreads = 1024, kHybKpt = 18;
+constexpr uint32_t kHybCapacity = kHybThreads * kHybKpt;  // keys one bucket may hold (18432)
+constexpr uint32_t kHybBuckets = kJointBins * kJointBins;
+constexpr uint32_t kHybSample = 65536;  // keys the gate reads, at a fixed stride over the whole input ...
+constexpr uint32_t kHybGateGroups = 64;  // ... by this many workgroups, each counting its own 1024
+// the gate's flag word: after the joint counts and the rows counter, inside the 16 bytes cleared with them
+constexpr uint32_t kHybGateFlag = kJointBins * kJointBins + 1;
+struct HybArgs {
+    const uint32_t *kin;     // gate: the sort's input; bucket phase: pass B's output
+    uint32_t *kout;          // bucket phase: the sort's output
+    uint32_t *joint;         // [digit 2][digit 3]: the joint counts, scanned in place into the bucket starts
+    uint32_t *bounds;        // pass B's chunks {kGroupsWhole, the digit-3 groups' starts[0..R]}
+    uint32_t *gflags;        // the sort's group bounds (rsort_group_flags): a hybrid sort reports {groups, none}
+    uint32_t *done;          // the check and report words
+    uint64_t n;
+    uint32_t threshold;      // gate: a top-16-bit bucket with this many sampled keys is skewed
+    uint32_t force;          // RSORT_HYBRID_FORCE: the gate reports its verdict and passes anyway
+    uint32_t rank_fault;
+};
+// gate -> joint[kHybGateFlag] != 0: skewed (the joint count then leaves at once: HistArgs::mode points at the
+// flag); bounds: clears the check words, writes the verdict and the mode word -- kHybLsd after a skewed verdict,
+// else kHybRun when the largest bucket fits kHybCapacity (joint scanned, bounds written) or kHybLsd (joint
+// cleared for the LSD passes' own joint count); bucket: the in-LDS finish, grid workgroups (grid-stride over the
+// buckets).
+hipError_t launch_hyb_gate(const HybArgs &a, hipStream_t s);
+hipError_t launch_hyb_bounds(const HybArgs &a, hipStream_t s);
+hipError_t launch_hyb_bucket(const HybArgs &a, uint32_t grid, hipStream_t s);
+// Lists the bucket kernel in rsort_scatter_kernels_used (called when a sort enqueues the hybrid launches, before
+// its first scatter: the record keeps first-use order and its readers take the last plain kernel as the pass's).
+void hyb_note_bucket();
+// Resident bucket-kernel workgroups per CU (occupancy query), 0 on error.
+int hyb_blocks_per_cu();
 
 // ------------------------------------------------------------------------------ segmented sort
 // (rsort_segmented.hip; rsort_u32_segmented_device.) Four kernels by segment length. Up to kSegWaveKeys keys ONE

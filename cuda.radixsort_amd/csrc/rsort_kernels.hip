@@ -83,6 +83,16 @@ void note_used(const void *fn) {
 }
 }  // namespace
 
+void note_kernel_used(const void *fn, const char *name) {
+    {
+        std::lock_guard<std::mutex> g(g_kn_mu);
+        bool known = false;
+        for (auto &kv : g_kn_names) known = known || kv.first == fn;
+        if (!known) g_kn_names.emplace_back(fn, std::string(name));
+    }
+    note_used(fn);
+}
+
 size_t scatter_kernels_used(char *buf, size_t len, int reset) {
     std::lock_guard<std::mutex> g(g_kn_mu);
     std::string out;
@@ -211,7 +221,7 @@ __device__ __forceinline__ void hist_joint_body(const HistArgs &a, uint32_t *s_j
     }
     for (uint32_t i = t; i < R; i += THREADS) s_nz[i] = 0u;
     __syncthreads();
-    const uint32_t s0 = a.shift, s1 = a.shift + kJointBits;
+    const uint32_t s0 = a.shift, s1 = a.shift2 != 0u ? a.shift2 : a.shift + kJointBits;  // (HistArgs::shift2)
     // add inc (<= 64) to the 16-bit counter of pair (d, e); the add that takes it to 2^15 moves 2^15
     // to the row's spill word and to the global count (the counter stays below 2^15 + 64)
     auto add_pair = [&](uint32_t d, uint32_t e, uint32_t inc) {
@@ -458,6 +468,7 @@ __global__ __launch_bounds__(THREADS) void rs_histogram(HistArgs a) {
     const uint32_t S = a.split;
     const uint32_t c = blockIdx.x / S;
     const uint32_t sub = blockIdx.x % S;
+    if (a.mode != nullptr && *a.mode != a.mode_want) return;  // hybrid-eligible sorts: the other route runs
     if (a.bounds != nullptr && a.bounds[0] == kGroupsWhole) {
         // digit-group chunks: this pass's table is the previous pass's joint counts
         const uint64_t m = (uint64_t)R * a.num_chunks;
@@ -471,6 +482,11 @@ __global__ __launch_bounds__(THREADS) void rs_histogram(HistArgs a) {
     if (a.done != nullptr && blockIdx.x == 0 && t == 0) {
         a.done[0] = 0u;
         a.done[kDoneErr] = 0u;
+        // (the hybrid route's report, rsort_hybrid_report: this sort was not eligible)
+        a.done[kHybMode] = kHybLsd;
+        a.done[kHybGate] = kGateNone;
+        a.done[kHybMax] = 0u;
+        a.done[kHybEligible] = 0u;
     }
     if constexpr (JOINT) {
         if (a.joint_enable == nullptr || *a.joint_enable != kGroupsFixed) {
@@ -663,6 +679,7 @@ __global__ __launch_bounds__(THREADS) void rs_histogram(HistArgs a) {
 // L2) and scans itself.
 __global__ __launch_bounds__(kScanThreads) void rs_scan_reduce(ScanArgs a) {
     __shared__ uint32_t s_ws[kScanThreads / kWave];
+    if (a.mode != nullptr && *a.mode != a.mode_want) return;  // hybrid-eligible sorts: the other route runs
     // next-digit plans: clear the table the coming scatter counts into (read by the previous
     // pass's scatter, finished before this launch)
     for (uint64_t i = (uint64_t)blockIdx.x * kScanThreads + threadIdx.x; i < a.zero_n; i += (uint64_t)gridDim.x * kScanThreads)
@@ -738,6 +755,7 @@ __global__ __launch_bounds__(kScanThreads) void rs_scan_reduce(ScanArgs a) {
 __global__ __launch_bounds__(kScanThreads) void rs_scan_down(ScanArgs a) {
     __shared__ uint32_t s_ws[kScanThreads / kWave];
     const uint32_t b = blockIdx.x;
+    if (a.mode != nullptr && *a.mode != a.mode_want) return;  // hybrid-eligible sorts: the other route runs
     uint32_t pre = 0;
     for (uint32_t i = threadIdx.x; i < b; i += kScanThreads) pre += a.block_sums[i];
     uint32_t prefix;
@@ -888,7 +906,8 @@ __global__ __launch_bounds__(1024) void rs_joint_bounds(const uint32_t *joint, c
                                                         uint32_t *bounds, uint32_t *plan, uint32_t *pcounts,
                                                         uint64_t n, uint64_t max_keys, uint32_t snap,
                                                         uint32_t weighted, const uint32_t *ctab,
-                                                        uint32_t *rows_cnt, const uint32_t *rowone) {
+                                                        uint32_t *rows_cnt, const uint32_t *rowone,
+                                                        const uint32_t *mode, uint32_t mode_want) {
     constexpr uint32_t R = kJointBins;
     constexpr uint32_t Q = 1024 / R;
     __shared__ uint32_t s_part[Q][R];
@@ -905,6 +924,7 @@ __global__ __launch_bounds__(1024) void rs_joint_bounds(const uint32_t *joint, c
     __shared__ uint32_t s_slot[R];                 // counted pieces' slots
     __shared__ uint32_t s_rows;                    // every chunk wrote its joint-count rows
     const uint32_t t = threadIdx.x;
+    if (mode != nullptr && *mode != mode_want) return;  // hybrid-eligible sorts: the other route runs
     if (t < 4) bounds[kBoundsStat + t] = 0u;       // (the cut plan's stats: none unless one is made below)
     if (t == 0) {
         // (read and re-armed for the next joint count; the other threads read s_rows after a barrier)
@@ -1651,6 +1671,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? hooks::kLinesMinWavesSmal
     // clustered-pass selection (ScatterArgs::cl_select): the plain and the clustered kernel are both
     // launched, and the one not selected by the device-side flag leaves at once
     if (a.cl_select != nullptr && ((*a.cl_select != kGroupsWhole) != (CL != 0))) return;
+    if (a.mode != nullptr && *a.mode != a.mode_want) return;  // hybrid-eligible sorts: the other route runs
     RS_WG_T0
     if (a.bounds != nullptr && a.bounds[0] != 0u) {
         // digit-group chunk (rs_histogram_joint): any start, so the tiles start at the 256-B
@@ -2934,7 +2955,8 @@ hipError_t launch_scatter(int bits, int pairs, int rank_algo, int dmode, int geo
     // other kernel would read the unscanned counts (or the group bounds) as offsets -- refuse, never
     // sort wrongly
     const bool lines = is_line_kernel(fn);
-    if ((a.raw_table || a.next_table != nullptr || a.bounds != nullptr) && !lines) return hipErrorInvalidValue;
+    if ((a.raw_table || a.next_table != nullptr || a.bounds != nullptr || a.mode != nullptr) && !lines)
+        return hipErrorInvalidValue;
     ScatterArgs copy = a;
     if (cl == nullptr) copy.cl_select = nullptr;  // no clustered variant: the plain kernel does the pass
     if (lines) {
@@ -2975,9 +2997,10 @@ hipError_t launch_histogram_joint(const HistArgs &a, hipStream_t s) {
 hipError_t launch_joint_bounds(const uint32_t *joint, const uint32_t *enable, uint32_t *bounds,
                                uint32_t *plan, uint32_t *pcounts, uint64_t n, uint64_t max_keys,
                                uint32_t snap, uint32_t weighted, hipStream_t s, const uint32_t *ctab,
-                               uint32_t *rows_cnt, const uint32_t *rowone) {
+                               uint32_t *rows_cnt, const uint32_t *rowone, const uint32_t *mode,
+                               uint32_t mode_want) {
     rs_joint_bounds<<<1, 1024, 0, s>>>(joint, enable, bounds, plan, pcounts, n, max_keys, snap, weighted, ctab,
-                                       rows_cnt, rowone);
+                                       rows_cnt, rowone, mode, mode_want);
     return hipGetLastError();
 }
 

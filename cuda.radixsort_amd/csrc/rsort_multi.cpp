@@ -502,7 +502,10 @@ int multi_sort(const uint32_t *d_keys, const uint32_t *d_vals, int64_t n, uint32
         if (n > 0) {
             rsort_plan p;
             if ((st = rsort_plan_make(n, k_bits, pairs, 0, &p))) return st;
-            if ((st = rsort_sort_planned(&p, d_keys, d_vals, d_keys_out, d_vals_out, m.sub, m.sub_bytes, s))) return st;
+            // (the multi-GPU path's local sorts never take the hybrid route: said here, not left to its gate)
+            if ((st = rsort_sort_planned_ex(&p, d_keys, d_vals, d_keys_out, d_vals_out, m.sub, m.sub_bytes, s,
+                                            RSORT_SORT_NO_HYBRID)))
+                return st;
         }
         *out_n = n;
         *out_offset = 0;
@@ -750,7 +753,8 @@ int multi_sort(const uint32_t *d_keys, const uint32_t *d_vals, int64_t n, uint32
             if (h + 1 < H && side && hipEventRecord(side->ready, s) == hipSuccess &&
                 hipStreamWaitEvent(side->s, side->ready, 0) == hipSuccess)
                 ss = side->s;  // sorted while the next half is exchanged on `s`
-            if ((st = rsort_sort_planned(&p, ok, ov, ok, ov, m.sub, m.sub_bytes, ss))) return st;
+            // (a rank's keys cover 1 / N of the key space: their (digit 3, digit 2) buckets would overflow)
+            if ((st = rsort_sort_planned_ex(&p, ok, ov, ok, ov, m.sub, m.sub_bytes, ss, RSORT_SORT_NO_HYBRID))) return st;
             if (ss != s) {
                 if (hipEventRecord(side->done, side->s) != hipSuccess) return RSORT_ERR_HIP;
                 side_pending = true;  // (the next half's own copy then stays on `s`)

@@ -57,7 +57,7 @@ class GpuOps:
 
     def sort_keys(self, keys):
         p = rs.plan(keys.numel(), 8, False)
-        rs.sort_device(keys, keys, 8, ws=self._workspace(p.workspace_bytes), plan_=p)
+        rs.sort_device(keys, keys, 8, ws=self._workspace(p.workspace_bytes), plan_=p, hybrid=False)
         return keys
 
     def partition(self, keys, vals, splitters):
@@ -75,7 +75,7 @@ class GpuOps:
         n = keys.numel()
         p = rs.plan(n, k_bits, vals is not None)
         rs.sort_device(keys, keys, k_bits, vals_in=vals, vals_out=vals, ws=self._workspace(p.workspace_bytes),
-                       plan_=p)
+                       plan_=p, hybrid=False)  # (a rank's keys cover 1 / N of the key space)
         return keys, vals
 
 

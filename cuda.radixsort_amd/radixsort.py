@@ -167,6 +167,13 @@ SIGNATURES = {
     "rsort_u32_device": ([_vp, _vp, _i64, _int, _vp, _sz, _vp], _int),
     "rsort_u32_pairs_device": ([_vp, _vp, _vp, _vp, _i64, _int, _vp, _sz, _vp], _int),
     "rsort_sort_planned": ([_PP, _vp, _vp, _vp, _vp, _vp, _sz, _vp], _int),
+    "rsort_sort_planned_ex": ([_PP, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _int], _int),
+    "rsort_set_hybrid": ([_int], _int),
+    "rsort_get_hybrid": ([], _int),
+    "rsort_hybrid_capacity": ([], _int),
+    "rsort_hybrid_range": ([ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _int),
+    "rsort_hybrid_gate_threshold": ([_i64], _int),
+    "rsort_hybrid_report": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p], _int),
     "rsort_u32": ([_vp, _vp, _i64, _int], _int),
     "rsort_u32_ex": ([_vp, _vp, _i64, _int, _int, ctypes.POINTER(PhaseTimes)], _int),
     "rsort_u32_pairs": ([_vp, _vp, _vp, _vp, _i64, _int], _int),
@@ -374,17 +381,75 @@ def workspace(nbytes: int, device="cuda"):
 
 
 def sort_device(keys_in, keys_out, k_bits=8, vals_in=None, vals_out=None, ws=None, stream=None,
-                plan_: Plan | None = None):
-    """Stream-ordered device sort of torch int32/uint32 tensors (bits = u32 keys)."""
+                plan_: Plan | None = None, hybrid: bool = True):
+    """Stream-ordered device sort of torch int32/uint32 tensors (bits = u32 keys). hybrid=False keeps
+    this sort off the hybrid route (RSORT_SORT_NO_HYBRID) whatever set_hybrid says."""
     n = keys_in.numel()
     pairs = vals_in is not None
     p = plan_ if plan_ is not None else plan(n, k_bits, pairs)
     if ws is None:
         ws = workspace(p.workspace_bytes, keys_in.device)
-    _check(_lib().rsort_sort_planned(ctypes.byref(p), _ptr(keys_in), _ptr(vals_in), _ptr(keys_out),
-                                     _ptr(vals_out), _ptr(ws), ws.numel(), _stream(stream)),
-           "rsort_sort_planned")
+    if hybrid:
+        _check(_lib().rsort_sort_planned(ctypes.byref(p), _ptr(keys_in), _ptr(vals_in), _ptr(keys_out),
+                                         _ptr(vals_out), _ptr(ws), ws.numel(), _stream(stream)),
+               "rsort_sort_planned")
+    else:
+        _check(_lib().rsort_sort_planned_ex(ctypes.byref(p), _ptr(keys_in), _ptr(vals_in), _ptr(keys_out),
+                                            _ptr(vals_out), _ptr(ws), ws.numel(), _stream(stream), SORT_NO_HYBRID),
+               "rsort_sort_planned_ex")
     return keys_out
+
+
+SORT_NO_HYBRID = 1
+HYBRID_AUTO, HYBRID_OFF, HYBRID_FORCE = 0, 1, 2
+GATE_NONE, GATE_PASS, GATE_SKEWED = 0, 1, 2
+
+
+def set_hybrid(mode: int):
+    """The hybrid route of keys-only k = 8 sorts (rsort_set_hybrid; process-wide): HYBRID_AUTO (default),
+    HYBRID_OFF (the LSD passes exactly), HYBRID_FORCE (test hook: no n range, the gate only reports)."""
+    _check(_lib().rsort_set_hybrid(int(mode)), "rsort_set_hybrid")
+
+
+def get_hybrid() -> int:
+    return int(_lib().rsort_get_hybrid())
+
+
+@contextmanager
+def hybrid(mode: int):
+    old = get_hybrid()
+    set_hybrid(mode)
+    try:
+        yield
+    finally:
+        set_hybrid(old)
+
+
+def hybrid_capacity() -> int:
+    """Keys one (digit 3, digit 2) bucket may hold for the hybrid route to run."""
+    return int(_lib().rsort_hybrid_capacity())
+
+
+def hybrid_range() -> tuple[int, int]:
+    """The automatic n range of the hybrid route (inclusive)."""
+    lo, hi = _i64(), _i64()
+    _check(_lib().rsort_hybrid_range(ctypes.byref(lo), ctypes.byref(hi)), "rsort_hybrid_range")
+    return int(lo.value), int(hi.value)
+
+
+def hybrid_gate_threshold(n: int) -> int:
+    t = int(_lib().rsort_hybrid_gate_threshold(int(n)))
+    if t < 0:
+        raise RSortError(-t, "rsort_hybrid_gate_threshold")
+    return t
+
+
+def hybrid_report(p: Plan, ws, stream=None) -> dict:
+    """rsort_hybrid_report of the last sort with plan `p` and workspace `ws` (synchronises the stream):
+    {eligible, gate (GATE_*), max_bucket, hybrid (the route that sorted the keys)}."""
+    r = (ctypes.c_int * 4)()
+    _check(_lib().rsort_hybrid_report(ctypes.byref(p), _ptr(ws), r, _stream(stream)), "rsort_hybrid_report")
+    return {"eligible": bool(r[0]), "gate": int(r[1]), "max_bucket": int(r[2]), "hybrid": bool(r[3])}
 
 
 def group_flags(p: Plan, ws, stream=None) -> list[int]:

@@ -138,6 +138,13 @@ RSORT_API int rsort_u32_pairs_device(const uint32_t *d_keys_in, const uint32_t *
                                      int k_bits, void *d_workspace, size_t workspace_bytes,
                                      void *stream);
 /* Same, with an explicit plan (from rsort_plan_make) -- lets tests pin the geometry. */
+/* rsort_sort_planned with flags: RSORT_SORT_NO_HYBRID keeps this sort off the hybrid route (rsort_set_hybrid)
+ * whatever the process-wide setting says. */
+#define RSORT_SORT_NO_HYBRID 1
+RSORT_API int rsort_sort_planned_ex(const rsort_plan *plan, const uint32_t *d_keys_in,
+                                    const uint32_t *d_vals_in, uint32_t *d_keys_out,
+                                    uint32_t *d_vals_out, void *d_workspace, size_t workspace_bytes,
+                                    void *stream, int flags);
 RSORT_API int rsort_sort_planned(const rsort_plan *plan, const uint32_t *d_keys_in,
                                  const uint32_t *d_vals_in, uint32_t *d_keys_out,
                                  uint32_t *d_vals_out, void *d_workspace, size_t workspace_bytes,
@@ -248,6 +255,63 @@ RSORT_API int rsort_get_rank_algo(void);
  * Off: every pass counts its own histogram. Same output either way; process-wide. */
 RSORT_API int rsort_set_group_chunks(int enable);
 RSORT_API int rsort_get_group_chunks(void);
+/* The hybrid route: keys-only k = 8 sorts read and write the keys three times instead of four.
+ *
+ * One joint histogram counts the 65536 (digit 3, digit 2) pairs; two MSD scatter passes (by digit 3 over fixed
+ * chunks, by digit 2 over the digit-3 groups -- the same whole-line scatter kernel as the LSD passes) leave the
+ * keys in 65536 contiguous buckets ordered by their top 16 bits; one kernel then sorts each bucket by its low 16
+ * bits inside LDS (two 8-bit counting passes, lane-ordered ranks with the per-wave rank check) and writes it
+ * once. The output of a keys-only sort is unique, so it is bit-identical to the LSD passes' output.
+ *
+ * A sort is ELIGIBLE (decided on the host, per call) when it is keys-only with k = 8, its plan has the 256 chunks
+ * of line tiles of the digit-group path and that path is on (rsort_set_group_chunks, the default ranking with a
+ * passed lane-order probe, both key outputs 4-B aligned with positions below 2^32), in != out (the route goes
+ * in -> out -> workspace -> out and never writes `in`; an in-place sort stays on the LSD passes and pays no
+ * staging copy), and n lies in the automatic range (rsort_hybrid_range: from the measured break-even size up to
+ * where the mean bucket n / 65536 reaches rsort_hybrid_capacity()). rsort_u32_multi*'s local sorts and
+ * partitions never are (a rank's keys cover 1 / N of the key space).
+ *
+ * An eligible sort decides the route ON THE DEVICE, with no host synchronisation, in two steps:
+ *   1. the sample gate: one small launch (~5 us) reads 65536 keys at a fixed stride over the whole input, 64
+ *      workgroups of 1024 keys, each counting the top-16-bit buckets of its 64th of the input; a bucket holding
+ *      rsort_hybrid_gate_threshold(n) of a workgroup's 1024 keys (7 at 2^30 keys) -- a count a bucket within the
+ *      capacity reaches less than once in a billion sorts (Poisson tail), i.e. a bucket of ~0.7 % of that part of
+ *      the input, hundreds of times the capacity's share -- says SKEWED and the sort takes the LSD passes with no
+ *      extra key read. Zipf, hot-key, all-equal and small-integer keys end here (and so may an input each 64th
+ *      of which is clustered in a few buckets although the whole is balanced).
+ *   2. the exact count: the joint histogram gives every bucket's size; the hybrid runs when the largest is at
+ *      most rsort_hybrid_capacity() keys, else the LSD passes do -- and this sort has read the keys once more
+ *      than an ineligible one (one histogram read, ~8 % of the LSD sort's time at 2^30 keys). The inputs that pay
+ *      it: moderately skewed ones, whose largest top-16-bit bucket is above the capacity but holds less than
+ *      ~0.7 % of the keys (e.g. keys drawn from a few thousand distinct 16-bit prefixes, or uniform keys with
+ *      one prefix twice as likely as the rest).
+ * Both kernel sequences are enqueued; every kernel tests the device-side mode word and those of the route not
+ * taken leave at once (about two dozen empty launches when the hybrid runs, seven when the LSD passes do).
+ *
+ * rsort_set_hybrid (process-wide): RSORT_HYBRID_AUTO (default) as above; RSORT_HYBRID_OFF: no sort is eligible,
+ * exactly the LSD passes; RSORT_HYBRID_FORCE (a test hook): the n range and the gate's verdict are ignored (the
+ * gate still runs and reports), never the exact capacity check. */
+#define RSORT_HYBRID_AUTO 0
+#define RSORT_HYBRID_OFF 1
+#define RSORT_HYBRID_FORCE 2
+RSORT_API int rsort_set_hybrid(int mode);
+RSORT_API int rsort_get_hybrid(void);
+/* Keys one (digit 3, digit 2) bucket may hold for the hybrid route to run (18432). */
+RSORT_API int rsort_hybrid_capacity(void);
+/* The automatic n range of the hybrid route, both ends inclusive. */
+RSORT_API int rsort_hybrid_range(int64_t *min_keys, int64_t *max_keys);
+/* The sample gate's threshold for a sort of n keys (keys of one gate workgroup's 1024 in one top-16-bit bucket),
+ * or -RSORT_ERR_SIZE. */
+RSORT_API int rsort_hybrid_gate_threshold(int64_t n);
+/* After a sort with `plan` and `d_workspace` has completed on `stream`: report[0] = 1 if the sort was eligible,
+ * report[1] = the gate's verdict (RSORT_GATE_NONE: not eligible, RSORT_GATE_PASS, RSORT_GATE_SKEWED), report[2] =
+ * the largest bucket of the exact count (0 when it did not run), report[3] = 1 if the hybrid route sorted the
+ * keys, 0 if the LSD passes did. Synchronises the stream. After a hybrid sort rsort_group_flags reports {1, 0}:
+ * its second pass ran on the digit-3 groups and there is no fourth. */
+#define RSORT_GATE_NONE 0
+#define RSORT_GATE_PASS 1
+#define RSORT_GATE_SKEWED 2
+RSORT_API int rsort_hybrid_report(const rsort_plan *plan, const void *d_workspace, int *report, void *stream);
 /* After a sort with `plan` and `d_workspace` has completed on `stream`: flags[i] says how odd
  * pass 2i+1 took its chunks (i < 2): 1 = the digit groups, 2 = equal chunks cutting unbalanced
  * groups (counted pieces), 0 = fixed chunks with a counted histogram (group chunks off, or plans
@@ -307,7 +371,8 @@ RSORT_API int rsort_inject_rank_fault(int enable);
 /* The scatter kernel instantiations this library has launched since the last reset, ';'-joined
  * into buf (at most len - 1 characters and a NUL); returns the full length. reset != 0 clears the
  * record. A k = 8 digit-group sort launches a plain and a clustered-input kernel for each pass
- * after the first (the device picks one, the other leaves at once): both are listed. */
+ * after the first (the device picks one, the other leaves at once): both are listed. A hybrid-eligible sort
+ * (rsort_set_hybrid) lists the bucket kernel rs_bucket_sort16 too; rsort_hybrid_report says whether it worked. */
 RSORT_API size_t rsort_scatter_kernels_used(char *buf, size_t len, int reset);
 /* 1 if the current device's LDS returns same-address atomic adds in lane order (the default
  * ranking relies on it and falls back to ballots otherwise), 0 if not, < 0 on error. The
