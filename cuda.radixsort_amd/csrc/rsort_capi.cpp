@@ -484,10 +484,11 @@ int check_plan(const rsort_plan *p) {
 // ------------------------------------------------------------------------------ hybrid route
 // (rsort_hybrid.hip.) The automatic n range: from kHybMinKeys (measured: DESIGN §3, profiles/hybrid_ab.json;
 // RSORT_HYB_MIN_KEYS under RSORT_LAB=1 for A/B runs) up to where the MEAN bucket n / 65536 reaches the capacity.
-// The bucket phase pays ~4.7 us per bucket whatever its size (65536 buckets whatever n), so the route loses
-// at 2^29 keys (4.50 against 4.17 ms) and 2^28 (3.13 against 2.25) and wins from about 0.7 x 2^30 keys on:
-// 3 x 2^28 keys 5.96 against 6.17 ms (-3.5 %), 7 x 2^27 keys 6.76 against 7.19 (-6 %).
-constexpr int64_t kHybMinKeys = (int64_t)3 << 28;
+// The bucket phase pays a fixed cost per bucket (65536 buckets whatever n), which two resident workgroups per CU
+// overlap: the route now wins at every measured size -- 2^28 keys 2.17 against 2.27 ms (-4.5 %), 2^29 3.44 against
+// 4.15 (-17 %), 3 x 2^28 4.80 against 6.16 (-22 %), 7 x 2^27 5.48 against 7.13 (-23 %). The range starts at the
+// smallest size measured (tests/test_hybrid.py keeps it above 2^27, where the digit-group tests pin the LSD passes).
+constexpr int64_t kHybMinKeys = (int64_t)1 << 28;
 constexpr int64_t kHybMaxKeys = (int64_t)kHybCapacity * kHybBuckets;
 int64_t hyb_min_keys() {
     static const int64_t v = [] {
@@ -498,10 +499,19 @@ int64_t hyb_min_keys() {
     return v;
 }
 
-// Bucket-kernel workgroups per resident slot (grid-stride over the buckets): 2^30 uniform keys sorted in 7.733 ms
-// with 1, 7.680 with 2, 7.672 with 4 (same-box bench runs; a workgroup that ends early leaves its slot to a fresh
-// one instead of the slowest deciding).
-constexpr int kHybGridMult = 4;
+// Bucket-kernel workgroups per resident slot (grid-stride over the buckets; a workgroup that ends early leaves its
+// slot to a fresh one instead of the slowest deciding). 2^30 uniform keys, two resident workgroups per CU, same-box
+// bench runs: 6.52 ms with 1, 6.41 with 2, 6.33 with 4, 6.28 with 8 and with 16, 6.40 with 32 (DESIGN §3 "Hybrid
+// route"; RSORT_HYB_GRID_MULT under RSORT_LAB=1 for A/B runs).
+constexpr int kHybGridMult = 8;
+int hyb_grid_mult() {
+    static const int v = [] {
+        const char *e = lab_env("RSORT_HYB_GRID_MULT");
+        const int x = e ? atoi(e) : 0;
+        return (x >= 1 && x <= 256) ? x : kHybGridMult;
+    }();
+    return v;
+}
 
 // The sample gate's threshold. Each of the gate's kHybGateGroups workgroups reads m = min(n, kHybSample) /
 // kHybGateGroups keys at a fixed stride over its part of the input and counts them by their top 16 bits. A bucket
@@ -629,7 +639,7 @@ int sort_planned(const rsort_plan &p, const uint32_t *kin, const uint32_t *vin, 
         {
             const int cus = std::max(1, device_cus());
             const int bpc = std::max(1, hyb_blocks_per_cu());
-            const uint32_t grid = (uint32_t)std::min<int64_t>(kHybBuckets, (int64_t)cus * bpc * kHybGridMult);
+            const uint32_t grid = (uint32_t)std::min<int64_t>(kHybBuckets, (int64_t)cus * bpc * hyb_grid_mult());
             h.kin = c.tmp_k;
             PhaseScope ps(RSORT_PHASE_SCATTER, p.n, s, g_run);
             if ((st = hip_status(launch_hyb_bucket(h, grid, s)))) return st;
@@ -1126,6 +1136,11 @@ int rsort_set_hybrid(int mode) {
 int rsort_get_hybrid(void) { return g_hybrid.load(); }
 
 int rsort_hybrid_capacity(void) { return (int)kHybCapacity; }
+
+int rsort_hybrid_kernel_info(int *info) {
+    if (!info) return RSORT_ERR_ARG;
+    return hyb_kernel_info(info) == hipSuccess ? RSORT_OK : RSORT_ERR_HIP;
+}
 
 int rsort_hybrid_range(int64_t *min_keys, int64_t *max_keys) {
     if (!min_keys || !max_keys) return RSORT_ERR_ARG;

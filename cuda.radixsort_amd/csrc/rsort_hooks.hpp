@@ -42,4 +42,10 @@ __device__ __forceinline__ void store_word(uint32_t *p, uint32_t v) { *p = v; }
 #define RS_STAMP_DECL
 #define RS_STAMP(i)
 #define RS_STAMP_FLUSH()
+// per-phase cycle totals of the bucket kernel (rs_bucket_sort16, rsort_hybrid.hip): none in the library
+#define RS_HYB_STAMP_DECL
+#define RS_HYB_STAMP(i)
+#define RS_HYB_STAMP_LOADED(i)
+#define RS_HYB_STAMP_BUCKET()
+#define RS_HYB_STAMP_FLUSH()
 #endif

@@ -16,12 +16,14 @@
 //   rs_bucket_sort16 one workgroup per bucket (grid-stride): the bucket's keys share their top 16 bits and are
 //                    sorted by the low 16 in two 8-bit counting passes inside LDS (the product form of
 //                    dev/msd_lab.hip's bucket_sort16, grown from rs_seg_lds: padded whole-wave slots, lane-
-//                    ordered ranks with the per-wave rank check), one read and one write of the keys
+//                    ordered ranks with the per-wave rank check), one read and one write of the keys; only the
+//                    low halves are kept (packed registers, a 16-bit LDS tile), two workgroups resident per CU
 //
 // Every kernel of both routes tests the mode word (done[kHybMode]) and leaves at once when the other route
 // runs: no host synchronisation picks the route.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include "rsort_device.hpp"
 #include "rsort_hooks.hpp"
@@ -31,7 +33,6 @@ namespace rsort {
 
 namespace {
 
-constexpr uint32_t kPadKey = 0xFFFFFFFFu;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------------------ sample gate
@@ -157,112 +158,178 @@ __global__ __launch_bounds__(1024) void rs_hyb_bounds(HybArgs a) {
 }
 
 // ------------------------------------------------------------------------------ bucket phase
+// A wave-uniform value the compiler may not trace back: the tests `j < slots` of each unrolled loop are then a
+// scalar compare and branch where they stand. Without it the 18 results are computed once per bucket and kept as
+// 64-bit lane masks over all loops (36 SGPRs, which spilled).
+__device__ __forceinline__ uint32_t fresh_scalar(uint32_t x) {
+    x = __builtin_amdgcn_readfirstlane(x);  // (folded away where x is in an SGPR already)
+    asm volatile("" : "+s"(x));
+    return x;
+}
+// The same for a per-lane value: addresses made of it are computed where they are used, not once before the
+// bucket loop and held in registers through it.
+__device__ __forceinline__ uint32_t fresh_vector(uint32_t x) {
+    asm volatile("" : "+v"(x));
+    return x;
+}
+
 // Bucket b = (digit 3, digit 2) = (b >> 8, b & 255) is keys [start(b), start(b + 1)) of pass B's output.
 // Wave w holds keys [w * span, (w + 1) * span) of the bucket, slot j its keys w * span + 64 j + lane (span: the
-// bucket's share per wave in whole slots), the missing keys of the last slot being 0xFFFFFFFF pads that every
-// pass ranks last (rsort_segmented.hip, "Partial slots"): every ranked slot is a whole wave.
-// (Measured and not kept, dev/LOG.md: loading the next bucket's keys into the dead key registers while this one
-// is stored -- no gain, the phase waits on its LDS passes and barriers, not on HBM.)
+// bucket's share per wave in whole slots), the missing keys of the last slot being pads that every pass ranks
+// last (rsort_segmented.hip, "Partial slots"): every ranked slot is a whole wave.
+//
+// All keys of a bucket share their top 16 bits = b, so only the low halves are kept: slots 2 i and 2 i + 1 of a
+// thread in the two halves of one register (KPT / 2 registers), their ranks (below 64 KPT per wave) packed the
+// same way, and the tile the passes stage into holds 16-bit entries (36 KiB for 18432 keys). The output widens
+// each entry with b << 16 again. A key that pass A or B had put into the wrong bucket would so come out as
+// another key: every loaded key's top half is compared with b (kCheckTable in the check word). Pads are 0xFFFF;
+// they sit in the bucket's last slot, so a real key ending in 0xFFFF ranks before them in both passes.
+//
+// With 64 VGPRs and 53 KiB of LDS two 1024-thread workgroups are resident per CU (kHybResident; tested through
+// rsort_hybrid_kernel_info): one ranks while the other waits for its loads or at a barrier. Barriers per
+// counting pass: ranks -> column prefix (the first 256 threads, 16 counts each held in registers over the next
+// one) -> s_ws -> rows written -> staged; the read-back of pass 0 and the output need none of their own (the
+// next write of the tile comes three barriers later).
 template <int THREADS, int KPT>
-__global__ __launch_bounds__(THREADS) void rs_bucket_sort16(HybArgs a) {
-    constexpr int W = THREADS / kWave;
+__global__ __launch_bounds__(THREADS, kHybResident *THREADS / 256) void rs_bucket_sort16(HybArgs a) {
+    constexpr int W = THREADS / kWave, KP = KPT / 2, SW = 256 / kWave;
     constexpr uint32_t CAP = THREADS * KPT;
     static_assert(CAP == kHybCapacity && CAP % kWave == 0, "the capacity the exact count checks");
-    __shared__ __attribute__((aligned(16))) uint32_t s_k[CAP + 4];
+    static_assert(KPT % 2 == 0 && KPT * kWave <= 65536 && CAP <= 65536, "ranks and positions in 16 bits");
+    static_assert(THREADS >= 256, "one thread per digit in the column prefix");
+    __shared__ __attribute__((aligned(16))) uint16_t s_k[CAP + 8];
     __shared__ uint32_t s_cnt[W * 256];
-    __shared__ uint32_t s_ws[W];
+    __shared__ uint32_t s_ws[SW];
     if (a.done[kHybMode] != kHybRun) return;
-    const uint32_t t = threadIdx.x, w = t / kWave, lane = lane_id();
+    RS_HYB_STAMP_DECL
+    const uint32_t t = threadIdx.x, lane = lane_id();
+    const uint32_t w = __builtin_amdgcn_readfirstlane(t / kWave);  // (a scalar: the slot tests stay on the SALU)
     uint32_t *row = &s_cnt[w * 256];
-    uint32_t order_bad = 0, size_bad = 0;
-    // bucket b's start and size (0 past the last bucket; a bucket above the capacity -- the exact count rules
-    // it out -- is skipped and recorded, never staged)
-    auto bucket = [&](uint32_t b, uint32_t &s, uint32_t &n) {
-        s = 0u;
-        n = 0u;
-        if (b >= kHybBuckets) return;
-        s = a.joint[(b & 255u) * kJointBins + (b >> 8)];
+    uint32_t order_bad = 0, table_bad = 0;
+    for (uint32_t b = blockIdx.x; b < kHybBuckets; b += gridDim.x) {
+        // the bucket's start and size (a bucket above the capacity -- the exact count rules it out -- is skipped
+        // and recorded, never staged)
+        const uint32_t s = a.joint[(b & 255u) * kJointBins + (b >> 8)];
         const uint32_t b1 = b + 1u;
         const uint32_t e = b1 < kHybBuckets ? a.joint[(b1 & 255u) * kJointBins + (b1 >> 8)] : (uint32_t)a.n;
-        n = e - s;
+        uint32_t n = e - s;
         if (e < s || n > CAP || (uint64_t)e > a.n) {
-            size_bad = 1u;
+            table_bad = 1u;
             n = 0u;
         }
-    };
-    auto span_of = [&](uint32_t n) { return ((((n + 63u) / 64u) + W - 1) / W) * 64u; };
-    uint32_t key[KPT];
-    auto load = [&](uint32_t s, uint32_t n) {
-        const uint32_t span = span_of(n), i0 = w * span + lane;
+        const uint32_t span = ((((n + 63u) / 64u) + W - 1) / W) * 64u, base = w * span;
+        // slots of this wave that hold a key (the last may hold pads too), and whether its first is full
+        const uint32_t slots0 = base < n ? (min(span, n - base) + 63u) / 64u : 0u;
+        const bool full0 = base + kWave <= n;
+        const uint32_t hi = b << 16;
+        uint32_t key[KP];
+        {
+            // (every load of a live slot is in bounds: the lanes past n of the bucket's last slot read its last key)
+            const uint32_t left = base < n ? n - base : 0u;  // keys from this wave's first on
+            const uint32_t *in = a.kin + s + base;
+            const uint32_t slots = fresh_scalar(slots0), ll = fresh_vector(lane);
+            uint32_t diff = 0;
 #pragma unroll
-        for (int j = 0; j < KPT; ++j) {
-            const uint32_t i = i0 + j * kWave;
-            const bool in = (uint32_t)(j * kWave) < span && i < n;
-            key[j] = in ? __builtin_nontemporal_load(a.kin + s + i) : kPadKey;
+            for (int i = 0; i < KP; ++i) {
+                uint32_t k[2] = {hi | 0xFFFFu, hi | 0xFFFFu};
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const uint32_t j = 2 * i + h, x = j * kWave + ll;
+                    if (j < slots) {
+                        const uint32_t v = __builtin_nontemporal_load(in + min(x, left - 1u));
+                        k[h] = x < left ? v : k[h];
+                    }
+                    diff |= k[h] ^ hi;
+                }
+                key[i] = (k[0] & 0xFFFFu) | (k[1] << 16);
+            }
+            table_bad |= diff >> 16;
+            asm volatile("" : "+v"(table_bad));  // (here, or the 18 loaded words stay live to the end of the bucket)
         }
-    };
-    for (uint32_t b = blockIdx.x; b < kHybBuckets; b += gridDim.x) {
-        uint32_t s, n;
-        bucket(b, s, n);
-        load(s, n);
-        const uint32_t span = span_of(n), i0 = w * span + lane;
-        // s_k[ak + i] holds key i: quads of s_k are then 16-B aligned in kout (any 4-B-aligned base)
+        RS_HYB_STAMP_LOADED(0);
+        // s_k[ak + i] holds key i: quads of s_k (8 B) are then 16-B aligned in kout (any 4-B-aligned base)
         const uint32_t ak = (uint32_t)(((uintptr_t)(a.kout + s) >> 2) & 3u);
+        uint16_t *tile = s_k + ak;
+#pragma unroll 1
         for (int pass = 0; pass < 2; ++pass) {
             const uint32_t sh = pass * 8;
             for (uint32_t i = lane; i < 256; i += kWave) row[i] = 0;
-            uint32_t rk[KPT];
+            uint32_t rk[KP];
+            uint32_t slots = fresh_scalar(slots0);
 #pragma unroll
-            for (int j = 0; j < KPT; ++j) {
-                rk[j] = 0;
-                // (wave-uniform: the slot holds a key; its lanes past n hold pads)
-                if ((uint32_t)(j * kWave) < span && w * span + j * kWave < n) {
-                    const uint32_t d = (key[j] >> sh) & 255u;
-                    rk[j] = rank_add(row, d);
-                    if (j == 0 && w * span + kWave <= n) order_bad |= rank_check<8>(d, rk[j], a.rank_fault);
+            for (int i = 0; i < KP; ++i) {
+                rk[i] = 0;
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const uint32_t j = 2 * i + h;
+                    if (j < slots) {  // (wave-uniform: the slot holds a key; its lanes past n hold pads)
+                        const uint32_t d = (key[i] >> (16 * h + sh)) & 255u;
+                        uint32_t r = rank_add(row, d);
+                        if (j == 0 && full0) order_bad |= rank_check<8>(d, r, a.rank_fault);
+                        rk[i] |= r << (16 * h);
+                    }
                 }
             }
             __syncthreads();
-            // per digit: exclusive prefix over the waves' rows (in place), then over the digits
-            uint32_t tot = 0;
+            // per digit: the waves' counts become their exclusive prefix over the waves plus the digit's start
+            uint32_t c[W], tot = 0;
             if (t < 256) {
 #pragma unroll
                 for (int x = 0; x < W; ++x) {
-                    const uint32_t c = s_cnt[x * 256 + t];
-                    s_cnt[x * 256 + t] = tot;
-                    tot += c;
+                    c[x] = s_cnt[x * 256 + t];
+                    tot += c[x];
                 }
+                const uint32_t inc = wave_incl_scan(tot);
+                if (lane == kWave - 1) s_ws[w] = inc;
+                tot = inc - tot;
             }
-            uint32_t all;
-            const uint32_t dbase = block_excl_scan<THREADS>(t < 256 ? tot : 0u, s_ws, all);
+            __syncthreads();
             if (t < 256) {
 #pragma unroll
-                for (int x = 0; x < W; ++x) s_cnt[x * 256 + t] += dbase;
-            }
-            __syncthreads();
+                for (int x = 0; x < SW; ++x) tot += (uint32_t)x < w ? s_ws[x] : 0u;
 #pragma unroll
-            for (int j = 0; j < KPT; ++j) {
-                if ((uint32_t)(j * kWave) < span && w * span + j * kWave < n) {
-                    const uint32_t p = row[(key[j] >> sh) & 255u] + rk[j];  // (< roundup(n, 64) <= CAP)
-                    s_k[ak + p] = key[j];
+                for (int x = 0; x < W; ++x) {
+                    s_cnt[x * 256 + t] = tot;
+                    tot += c[x];
                 }
             }
+            __syncthreads();
+            slots = fresh_scalar(slots0);
+#pragma unroll
+            for (int i = 0; i < KP; ++i) {
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const uint32_t j = 2 * i + h;
+                    if (j < slots) {
+                        const uint32_t kh = key[i] >> (16 * h);
+                        const uint32_t p = row[(kh >> sh) & 255u] + ((rk[i] >> (16 * h)) & 0xFFFFu);  // (< roundup(n, 64))
+                        tile[p] = (uint16_t)kh;
+                    }
+                }
+            }
+            __syncthreads();
             if (pass == 0) {
-                __syncthreads();
+                // pass 1 ranks pass 0's output in position order (its stability is what sorts the bucket)
+                const uint16_t *mine = tile + base + lane;
+                slots = fresh_scalar(slots0);
 #pragma unroll
-                for (int j = 0; j < KPT; ++j) {
-                    if ((uint32_t)(j * kWave) < span && w * span + j * kWave < n) key[j] = s_k[ak + i0 + j * kWave];
+                for (int i = 0; i < KP; ++i) {
+                    uint32_t lo = 0xFFFFu, up = 0xFFFFu;
+                    if ((uint32_t)(2 * i) < slots) lo = mine[(2 * i) * kWave];
+                    if ((uint32_t)(2 * i + 1) < slots) up = mine[(2 * i + 1) * kWave];
+                    key[i] = lo | (up << 16);
                 }
             }
-            __syncthreads();
+            RS_HYB_STAMP(1 + pass);
         }
-        // out[s - ak + 4 q .. + 3] = s_k[4 q .. + 3]: whole quads inside the bucket as 16-B stores, the words at
-        // its two ends one by one
+        // out[s - ak + 4 q .. + 3] = b << 16 | s_k[4 q .. + 3]: whole quads inside the bucket as 16-B stores,
+        // the words at its two ends one by one
         {
             uint32_t *o = a.kout + s - ak;
             const uint32_t nq = (ak + n + 3u) / 4u;
-            for (uint32_t q = t; q < nq; q += THREADS) {
-                const u32x4 v = *reinterpret_cast<const u32x4 *>(&s_k[4 * q]);
+            for (uint32_t q = fresh_vector(t); q < nq; q += THREADS) {
+                const uint2 h2 = *reinterpret_cast<const uint2 *>(&s_k[4 * q]);
+                const u32x4 v = {hi | (h2.x & 0xFFFFu), hi | (h2.x >> 16), hi | (h2.y & 0xFFFFu), hi | (h2.y >> 16)};
                 if (4 * q >= ak && 4 * q + 4 <= ak + n) {
                     hooks::store_quad_nt(o + 4 * q, v);
                 } else {
@@ -272,9 +339,11 @@ __global__ __launch_bounds__(THREADS) void rs_bucket_sort16(HybArgs a) {
                 }
             }
         }
-        __syncthreads();
+        RS_HYB_STAMP(3);
+        RS_HYB_STAMP_BUCKET();
     }
-    if (a.done != nullptr && __ballot(size_bad != 0u) != 0ull && lane == 0) atomicOr(a.done + kDoneErr, kCheckTable);
+    RS_HYB_STAMP_FLUSH();
+    if (a.done != nullptr && __ballot(table_bad != 0u) != 0ull && lane == 0) atomicOr(a.done + kDoneErr, kCheckTable);
     report_order(a.done + kDoneErr, order_bad);
 }
 
@@ -301,13 +370,26 @@ hipError_t launch_hyb_bucket(const HybArgs &a, uint32_t grid, hipStream_t s) {
 }
 
 void hyb_note_bucket() {
-    note_kernel_used(bucket_kernel(), "rs_bucket_sort16<1024, 18>");
+    char name[48];
+    snprintf(name, sizeof(name), "rs_bucket_sort16<%d, %d>", kHybThreads, kHybKpt);
+    note_kernel_used(bucket_kernel(), name);
 }
 
 int hyb_blocks_per_cu() {
     int nb = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, bucket_kernel(), kHybThreads, 0) != hipSuccess) return 0;
     return nb;
+}
+
+hipError_t hyb_kernel_info(int info[4]) {
+    hipFuncAttributes fa{};
+    const hipError_t e = hipFuncGetAttributes(&fa, bucket_kernel());
+    if (e != hipSuccess) return e;
+    info[0] = kHybThreads;
+    info[1] = (int)fa.sharedSizeBytes;
+    info[2] = (int)fa.localSizeBytes;
+    info[3] = hyb_blocks_per_cu();
+    return hipSuccess;
 }
 
 }  // namespace rsort

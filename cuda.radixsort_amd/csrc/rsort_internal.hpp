@@ -297,7 +297,9 @@ constexpr uint32_t kCheckTable = 1u, kCheckRankOrder = 2u;
 constexpr uint32_t kHybMode = 4, kHybGate = 5, kHybMax = 6, kHybEligible = 7;
 constexpr uint32_t kHybLsd = 0, kHybRun = 2;                       // done[kHybMode]
 constexpr uint32_t kGateNone = 0, kGatePass = 1, kGateSkewed = 2;  // done[kHybGate]
-constexpr int kHybThreads = 1024, kHybKpt = 18;
+// the bucket kernel's shape, rs_bucket_sort16<kHybThreads, kHybKpt>, and the workgroups of it that a CU is to hold
+// at once (its register limit: kHybResident * kHybThreads / 256 waves per SIMD)
+constexpr int kHybThreads = 1024, kHybKpt = 18, kHybResident = 2;
 constexpr uint32_t kHybCapacity = kHybThreads * kHybKpt;  // keys one bucket may hold (18432)
 constexpr uint32_t kHybBuckets = kJointBins * kJointBins;
 constexpr uint32_t kHybSample = 65536;  // keys the gate reads, at a fixed stride over the whole input ...
@@ -329,6 +331,8 @@ hipError_t launch_hyb_bucket(const HybArgs &a, uint32_t grid, hipStream_t s);
 void hyb_note_bucket();
 // Resident bucket-kernel workgroups per CU (occupancy query), 0 on error.
 int hyb_blocks_per_cu();
+// rsort_hybrid_kernel_info: {threads per workgroup, static LDS bytes, scratch bytes per lane, hyb_blocks_per_cu()}
+hipError_t hyb_kernel_info(int info[4]);
 
 // ------------------------------------------------------------------------------ segmented sort
 // (rsort_segmented.hip; rsort_u32_segmented_device.) Four kernels by segment length. Up to kSegWaveKeys keys ONE

@@ -171,6 +171,7 @@ SIGNATURES = {
     "rsort_set_hybrid": ([_int], _int),
     "rsort_get_hybrid": ([], _int),
     "rsort_hybrid_capacity": ([], _int),
+    "rsort_hybrid_kernel_info": ([ctypes.POINTER(_int)], _int),
     "rsort_hybrid_range": ([ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _int),
     "rsort_hybrid_gate_threshold": ([_i64], _int),
     "rsort_hybrid_report": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p], _int),
@@ -428,6 +429,14 @@ def hybrid(mode: int):
 def hybrid_capacity() -> int:
     """Keys one (digit 3, digit 2) bucket may hold for the hybrid route to run."""
     return int(_lib().rsort_hybrid_capacity())
+
+
+def hybrid_kernel_info() -> dict:
+    """The hybrid route's bucket kernel: threads per workgroup, static LDS bytes, scratch bytes per lane and the
+    workgroups resident per CU on the current device (rsort_hybrid_kernel_info)."""
+    v = (_int * 4)()
+    _check(_lib().rsort_hybrid_kernel_info(v), "rsort_hybrid_kernel_info")
+    return {"threads": int(v[0]), "lds_bytes": int(v[1]), "scratch_bytes": int(v[2]), "resident_per_cu": int(v[3])}
 
 
 def hybrid_range() -> tuple[int, int]:

@@ -11,6 +11,8 @@
 //                             HW_ID (hwreg 4: cu 11:8, sh 12, se 15:13) over beg, XCC_ID (hwreg 20) over end
 //   RSORT_STAMPS              per-phase s_memtime cycle totals of thread 0 into ScatterArgs::stamps
 //                             [workgroup * 8 + phase] (rs_scatter_pairs, dev/pairs_lab.hip)
+//   RSORT_HYB_STAMPS          per-phase s_memtime cycle totals of rs_bucket_sort16's thread 0, summed over the
+//                             workgroups (rsort_hybrid.hip built with these hooks; dev/hyb_stamps.py)
 //   RSORT_LAB_NO_STORES       the scatter kernels' output stores compiled out (the values they would store kept
 //                             live): the LDS / VALU floor of a pass (DESIGN §3 "Floors"; the output is garbage)
 #pragma once
@@ -116,4 +118,44 @@ extern "C" __attribute__((visibility("default"), used)) int rsort_lab_wg_times(u
 #define RS_STAMP_DECL
 #define RS_STAMP(i)
 #define RS_STAMP_FLUSH()
+#endif
+
+// RSORT_HYB_STAMPS: rs_bucket_sort16's thread 0 adds the s_memtime cycles of each phase of every bucket it works
+// on to g_hyb_stamps[phase] (0 load issue + wait, 1 pass 0, 2 pass 1, 3 store issue, 7 buckets), summed over all
+// workgroups and launches since the last rsort_lab_hyb_stamps, which reads and clears them (dev/hyb_stamps.py).
+// RS_HYB_STAMP_LOADED waits for the loads first: without it the wait would be charged to pass 0.
+#ifdef RSORT_HYB_STAMPS
+namespace rsort {
+__device__ unsigned long long g_hyb_stamps[8];
+}
+extern "C" __attribute__((visibility("default"), used)) int rsort_lab_hyb_stamps(unsigned long long *host) {
+    const unsigned long long zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (hipDeviceSynchronize() != hipSuccess) return 6;
+    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(rsort::g_hyb_stamps), sizeof(zero)) != hipSuccess) return 6;
+    return hipMemcpyToSymbol(HIP_SYMBOL(rsort::g_hyb_stamps), zero, sizeof(zero)) == hipSuccess ? 0 : 6;
+}
+#define RS_HYB_STAMP_DECL unsigned long long hs_acc_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, hs_prev_ = __builtin_amdgcn_s_memtime();
+#define RS_HYB_STAMP(i)                                               \
+    do {                                                              \
+        const unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
+        hs_acc_[i] += now_ - hs_prev_;                                \
+        hs_prev_ = now_;                                              \
+    } while (0)
+#define RS_HYB_STAMP_LOADED(i)                                \
+    do {                                                      \
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      \
+        RS_HYB_STAMP(i);                                      \
+    } while (0)
+#define RS_HYB_STAMP_BUCKET() hs_acc_[7] += 1
+#define RS_HYB_STAMP_FLUSH()                                                                    \
+    do {                                                                                        \
+        if (threadIdx.x == 0)                                                                   \
+            for (int i_ = 0; i_ < 8; ++i_) atomicAdd(&rsort::g_hyb_stamps[i_], hs_acc_[i_]);    \
+    } while (0)
+#else
+#define RS_HYB_STAMP_DECL
+#define RS_HYB_STAMP(i)
+#define RS_HYB_STAMP_LOADED(i)
+#define RS_HYB_STAMP_BUCKET()
+#define RS_HYB_STAMP_FLUSH()
 #endif

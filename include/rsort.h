@@ -298,6 +298,11 @@ RSORT_API int rsort_set_hybrid(int mode);
 RSORT_API int rsort_get_hybrid(void);
 /* Keys one (digit 3, digit 2) bucket may hold for the hybrid route to run (18432). */
 RSORT_API int rsort_hybrid_capacity(void);
+/* The bucket kernel as built and as the current device holds it: info[0] = threads per workgroup, info[1] = its
+ * static LDS bytes, info[2] = its scratch (spill) bytes per lane, info[3] = workgroups of it resident per CU (the
+ * occupancy query the bucket grid is sized by). The kernel is written for two resident workgroups and no scratch;
+ * a build that loses either still sorts, slower. */
+RSORT_API int rsort_hybrid_kernel_info(int *info);
 /* The automatic n range of the hybrid route, both ends inclusive. */
 RSORT_API int rsort_hybrid_range(int64_t *min_keys, int64_t *max_keys);
 /* The sample gate's threshold for a sort of n keys (keys of one gate workgroup's 1024 in one top-16-bit bucket),
@@ -328,7 +333,11 @@ RSORT_API int rsort_cut_plan_stats(const rsort_plan *plan, const void *d_workspa
 /* After a sort with `plan` and `d_workspace` has completed on `stream`: *flags = 0 when every
  * on-device self-check of that sort passed; bit 0 (RSORT_CHECK_TABLE) = a k = 3, 4 pass found the
  * next-digit table it reads not holding n keys (the pass then wrote nothing; with RSORT_FEAT_TAIL_SCAN:
- * a tail scan found it so even after an acquire fence and a second sweep); bit 1 (RSORT_CHECK_RANK_ORDER)
+ * a tail scan found it so even after an acquire fence and a second sweep), or the hybrid route's bucket kernel
+ * found a bucket's bounds outside the capacity or the input, or a key whose top 16 bits are not its bucket's --
+ * the kernel keeps only the low halves and rebuilds the top half from the bucket index, so it compares EVERY key
+ * it loads (full 4-B loads) with that index: a key the two MSD passes misplaced is reported, never silently
+ * turned into another key; bit 1 (RSORT_CHECK_RANK_ORDER)
  * = a lane-ordered scatter kernel's per-tile rank check failed: the device no longer served the lanes of
  * a returning LDS add in lane order (the premise of the default ranking, rsort_lane_order_probe), so
  * equal digits may have been written out of order -- in either case the sort's output is not
