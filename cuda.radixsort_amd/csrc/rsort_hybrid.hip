@@ -148,6 +148,12 @@ __global__ __launch_bounds__(1024) void rs_hyb_bounds(HybArgs a) {
             run += v[i];
         }
     }
+    // rsort_cut_plan_stats: this route makes no cut plan (rs_joint_bounds stores these words on every other route;
+    // a workspace's content on entry is arbitrary -- tests/test_gpu_workspace_state.py, the hybrid_run case)
+    if (t < 4) {
+        a.gflags[kBoundsStat + t] = 0u;
+        a.gflags[kBoundsWords + kBoundsStat + t] = 0u;
+    }
     if (t == 0) {
         a.done[kHybMode] = kHybRun;
         a.done[kHybMax] = big;

@@ -377,6 +377,8 @@ def empty_u32(n, device="cuda"):
 
 
 def workspace(nbytes: int, device="cuda"):
+    """Device workspace of at least `nbytes` bytes. Its content is UNINITIALISED, on purpose: no entry point may
+    depend on what a workspace held before (include/rsort.h; tests/test_gpu_workspace_state.py)."""
     _need_torch()
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 

@@ -32,6 +32,8 @@
  *   - device entry points are stream-ordered on `stream` (a hipStream_t, NULL = the null
  *     stream), do no allocation, no host synchronisation and are graph-capturable; they use
  *     the caller's workspace (rsort_workspace_size bytes, any alignment >= 256 B);
+ *   - the workspace's content on entry is arbitrary (every word a call reads it has written first), and successive
+ *     calls of any plans and entry points may share one workspace on one stream;
  *   - the device is the caller's current HIP device.
  */
 #ifndef RSORT_H_
@@ -385,7 +387,8 @@ RSORT_API int rsort_inject_rank_fault(int enable);
 RSORT_API size_t rsort_scatter_kernels_used(char *buf, size_t len, int reset);
 /* 1 if the current device's LDS returns same-address atomic adds in lane order (the default
  * ranking relies on it and falls back to ballots otherwise), 0 if not, < 0 on error. The
- * probe runs once per device (a few microseconds) and is cached. */
+ * probe runs once per device (a few microseconds) and is cached. It allocates and synchronises: before a
+ * device entry is captured into a graph, call this (or one uncaptured sort) once on that device. */
 RSORT_API int rsort_lane_order_probe(void);
 /* Between begin and end, every launch made by this library records hipEvents around its
  * phases; end synchronises those events and returns the per-phase sums. */
