@@ -40,8 +40,6 @@ struct Gate {
     uint32_t want = 0;
 };
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // ------------------------------------------------------------------------------ profiler
 struct ProfRec {
     int phase;
@@ -97,6 +95,12 @@ struct PhaseScope {
 
 int hip_status(hipError_t e) { return e == hipSuccess ? RSORT_OK : RSORT_ERR_HIP; }
 
+// Copies `words` words of a workspace to the host, behind everything enqueued on s, and waits for them.
+int read_words(uint32_t *host, const uint32_t *dev, size_t words, hipStream_t s) {
+    if (hipMemcpyAsync(host, dev, words * 4, hipMemcpyDeviceToHost, s) != hipSuccess) return RSORT_ERR_HIP;
+    return hip_status(hipStreamSynchronize(s));
+}
+
 bool aligned4(const void *p) { return ((uintptr_t)p & 3u) == 0; }
 
 // The whole-line scatter kernels can write these outputs: any 4-B-aligned kout (launch_scatter
@@ -118,14 +122,20 @@ int device_cus() {
     return c;
 }
 
-// log2 of the smallest k = 4 keys-only sort on 1024-thread line tiles (default 28; RSORT_K4_LINES_LG
-// under RSORT_LAB=1 for A/B runs)
-int k4_lines_lg() {
-    static const int v = [] {
-        const char *e = lab_env("RSORT_K4_LINES_LG");
-        const int x = e ? atoi(e) : 0;
-        return (x >= 16 && x <= 32) ? x : 28;
-    }();
+// The planning and route lab switches (A/B runs under RSORT_LAB=1: lab_env), read once.
+struct Lab {
+    // log2 of the smallest k = 4 keys-only sort on 1024-thread line tiles
+    int k4_lines_lg = (int)lab_int("RSORT_K4_LINES_LG", 16, 32, 28);
+    // 0: cut plans with equal key counts per chunk
+    bool cut_weights = lab_flag("RSORT_CUT_WEIGHTS", true);
+    // 0: cut plans count all their pieces from the keys (no per-chunk joint-count rows; the round-4 scheme)
+    bool piece_rows = lab_flag("RSORT_PIECE_ROWS", true);
+    // 1: next-digit plans scan each pass's table in its last workgroup (the round-3 scheme) instead of every
+    // workgroup of the next pass summing the raw counts
+    bool nx_tail = lab_flag("RSORT_NX_TAIL", false);
+};
+const Lab &lab() {
+    static const Lab v;
     return v;
 }
 
@@ -145,7 +155,7 @@ int choose_geom(int64_t n, int k, int pairs, int rank, int partition, int cus) {
     if (k >= 5 && k <= 8 && !pairs && n >= enough * geom_tile_keys(kGeomLines)) return kGeomLines;
     // k = 4 keys from 2^28 on: the same 1024-thread line tiles (dev/scatter_lab LAB_K4 at 2^30:
     // 1.61 ms per pass against 1.75 ms with 4096-key tiles; at 2^26 0.120 against 0.113)
-    if (k == 4 && !pairs && n >= ((int64_t)1 << k4_lines_lg())) return kGeomLines;
+    if (k == 4 && !pairs && n >= ((int64_t)1 << lab().k4_lines_lg)) return kGeomLines;
     if (k >= 5 && k <= 8 && pairs && n >= enough * geom_tile_keys(kGeomLinesPairs)) return kGeomLinesPairs;
     // k = 3, 4 keys run 4096-key tiles through rs_scatter_lines (kGeomSmall's shape; whole 128-B
     // lines: 2^26 keys, k = 4: 0.117 vs 0.144 ms per pass, dev/scatter_lab.hip); k <= 2 keeps
@@ -161,41 +171,54 @@ bool joint_plan(const rsort_plan &p) {
            (geom_from_shape(p.threads, p.tile_keys, p.pairs) == (p.pairs ? kGeomLinesPairs : kGeomLines));
 }
 
-// RSORT_CUT_WEIGHTS=0 under RSORT_LAB=1: cut plans with equal key counts per chunk (A/B runs)
-bool cut_weights() {
-    static const bool v = [] {
-        const char *e = lab_env("RSORT_CUT_WEIGHTS");
-        return !(e != nullptr && e[0] == '0');
-    }();
-    return v;
-}
-
-// RSORT_PIECE_ROWS=0 under RSORT_LAB=1: cut plans count all their pieces from the keys (no per-chunk
-// joint-count rows; the round-4 scheme) for A/B runs
-bool piece_rows() {
-    static const bool v = [] {
-        const char *e = lab_env("RSORT_PIECE_ROWS");
-        return !(e != nullptr && e[0] == '0');
-    }();
-    return v;
-}
-
-// RSORT_NX_TAIL=1 under RSORT_LAB=1: next-digit plans scan each pass's table in its last workgroup
-// (the round-3 scheme) instead of every workgroup of the next pass summing the raw counts (A/B runs)
-bool nx_tail() {
-    static const bool v = [] {
-        const char *e = lab_env("RSORT_NX_TAIL");
-        return e != nullptr && e[0] != '\0' && e[0] != '0';
-    }();
-    return v;
-}
-
 // Next-digit counts (rs_scatter_lines, k = 3, 4 keys): each pass adds the next pass's chunk table
 // from where it writes every key, so only pass 0 reads keys for a histogram. Needs the line
 // kernel (lane-ordered ranks, line-capable outputs: checked per sort) and a second table.
 bool next_plan(const rsort_plan &p) {
     const int g = geom_from_shape(p.threads, p.tile_keys, p.pairs);
     return (p.k_bits == 3 || p.k_bits == 4) && !p.pairs && p.passes >= 2 && (g == kGeomSmall || g == kGeomLines);
+}
+
+// The workspace of a plan: THE statement of its layout (DESIGN §3 "Workspace state"). One walk gives every
+// region's pointer (nullptr where ws is: sizing) and the total, rsort_plan::workspace_bytes.
+struct Carve {
+    uint32_t *tmp_k, *tmp_v;  // ping-pong keys (and values)
+    uint32_t *table, *bsums;  // chunk x digit table, scan block sums
+    uint32_t *starts;         // bucket starts (partition / top histogram)
+    uint32_t *done;           // check words (tail-scan counter, check word, hybrid report: kDoneErr, kHyb*)
+    // digit-group plans (kJointRegionBytes; rows_cnt: the word behind the joint counts, cleared with them)
+    uint32_t *joint, *rows_cnt, *bounds, *plan, *pcounts, *rows;
+    uint32_t *table2, *table3;  // next-digit SORT plans: the next pass's table, the third of a raw-table rotation
+    size_t bytes;
+};
+
+Carve carve(const rsort_plan &p, void *ws, bool partition = false) {
+    Carve c{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        uint32_t *q = ws ? (uint32_t *)((char *)ws + off) : nullptr;
+        off += align256(bytes);
+        return q;
+    };
+    const size_t keys = (size_t)p.n * 4, table = (size_t)p.table_entries * 4;
+    c.tmp_k = take(keys);
+    if (p.pairs) c.tmp_v = take(keys);
+    c.table = take(table);
+    c.bsums = take((size_t)p.scan_blocks * 4);
+    c.starts = take((size_t)(p.bins + 1) * 4);
+    c.done = take(256);
+    if (joint_plan(p)) {
+        uint32_t **const region[] = {&c.joint, &c.bounds, &c.plan, &c.pcounts, &c.rows};
+        static_assert(sizeof(region) / sizeof(region[0]) == sizeof(kJointRegionBytes) / sizeof(kJointRegionBytes[0]), "");
+        for (size_t i = 0; i < sizeof(region) / sizeof(region[0]); ++i) *region[i] = take(kJointRegionBytes[i]);
+        if (c.joint) c.rows_cnt = c.joint + kJointBins * kJointBins;
+    }
+    if (!partition && next_plan(p)) {
+        c.table2 = take(table);
+        c.table3 = take(table);
+    }
+    c.bytes = off;
+    return c;
 }
 
 int plan_fill(int64_t n, int k, int pairs, int64_t tpc, rsort_plan *p, int partition = 0) {
@@ -230,24 +253,7 @@ int plan_fill(int64_t n, int k, int pairs, int64_t tpc, rsort_plan *p, int parti
     p->num_chunks = (tiles + tpc - 1) / tpc;
     p->table_entries = (int64_t)p->bins * p->num_chunks;
     p->scan_blocks = (p->table_entries + kScanSegment - 1) / kScanSegment;
-    size_t ws = align256((size_t)n * 4);                     // ping-pong keys
-    if (pairs) ws += align256((size_t)n * 4);                // ping-pong values
-    ws += align256((size_t)p->table_entries * 4);            // chunk x digit table
-    ws += align256((size_t)p->scan_blocks * 4);              // scan block sums
-    ws += align256((size_t)(p->bins + 1) * 4);               // bucket starts (partition / top hist)
-    ws += 256;                                               // check words (tail-scan counter, check word)
-    if (joint_plan(*p)) {
-        ws += align256((size_t)kJointBins * kJointBins * 4 + 4);  // joint counts [next digit][digit], rows counter
-        ws += align256((size_t)2 * kBoundsWords * 4);             // group bounds of passes 1 and 3
-        ws += align256((size_t)kPlanWords * 4);                   // cut plan
-        ws += align256((size_t)kPieceSlots * kJointBins * 4);     // its piece counts
-        ws += align256(((size_t)kRowsWords + kJointBins * kJointBins) * 4);  // per-chunk joint-count rows (64 MiB)
-    }
-    if (!partition && next_plan(*p)) {
-        ws += align256((size_t)p->table_entries * 4);  // the next pass's table
-        ws += align256((size_t)p->table_entries * 4);  // raw-table offsets: the third table of the rotation
-    }
-    p->workspace_bytes = ws;
+    p->workspace_bytes = carve(*p, nullptr, partition).bytes;
     return RSORT_OK;
 }
 
@@ -261,67 +267,16 @@ int partition_bits(int64_t n, int num_buckets, int pairs) {
     return bits;
 }
 
-struct Carve {
-    uint32_t *tmp_k, *tmp_v, *table, *bsums, *starts, *joint, *bounds, *plan, *pcounts, *table2, *done, *table3;
-    uint32_t *rows, *rows_cnt;  // joint plans: per-chunk joint-count rows (HistArgs::rows), their counter
+// ------------------------------------------------------------------------------ pass pieces
+// A launch = a builder (what every launch of the plan shares) + the optional fields its caller sets by name + a
+// runner (the launch-time decisions and the profiler's phase scope; the gate is the struct's own mode / mode_want).
+struct PassIo {
+    const uint32_t *kin, *vin;
+    uint32_t *kout, *vout;
 };
 
-Carve carve(const rsort_plan &p, void *ws) {
-    Carve c{};
-    char *q = (char *)ws;
-    c.tmp_k = (uint32_t *)q;
-    q += align256((size_t)p.n * 4);
-    if (p.pairs) {
-        c.tmp_v = (uint32_t *)q;
-        q += align256((size_t)p.n * 4);
-    }
-    c.table = (uint32_t *)q;
-    q += align256((size_t)p.table_entries * 4);
-    c.bsums = (uint32_t *)q;
-    q += align256((size_t)p.scan_blocks * 4);
-    c.starts = (uint32_t *)q;
-    q += align256((size_t)(p.bins + 1) * 4);
-    c.done = (uint32_t *)q;
-    q += 256;
-    if (joint_plan(p)) {
-        c.joint = (uint32_t *)q;
-        c.rows_cnt = c.joint + kJointBins * kJointBins;  // (cleared with the joint counts)
-        q += align256((size_t)kJointBins * kJointBins * 4 + 4);
-        c.bounds = (uint32_t *)q;
-        q += align256((size_t)2 * kBoundsWords * 4);
-        c.plan = (uint32_t *)q;
-        q += align256((size_t)kPlanWords * 4);
-        c.pcounts = (uint32_t *)q;
-        q += align256((size_t)kPieceSlots * kJointBins * 4);
-        c.rows = (uint32_t *)q;
-        q += align256(((size_t)kRowsWords + kJointBins * kJointBins) * 4);
-    }
-    if (next_plan(p)) {
-        c.table2 = (uint32_t *)q;
-        q += align256((size_t)p.table_entries * 4);
-        c.table3 = (uint32_t *)q;
-    }
-    return c;
-}
-
-// ------------------------------------------------------------------------------ pass pieces
-// Joint pass (pass p of a joint_plan counting for pass p + 1): one workgroup per chunk counts
-// this pass's table and the joint counts; then the chunks of pass p + 1 (its digit groups, or
-// the cut plan). enable: nullptr, or the previous odd pass's mode: the joint count runs after whole
-// digit groups and after a cut plan (both leave the joint counts cleared: the copy-mode histogram, the
-// cut plan's scan), not after fixed chunks. After a cut plan the input is clustered: the joint count
-// adds runs of equal pairs once (rs_histogram's run path), so pass 3 gets its own cut plan too.
-int do_histogram_joint(const rsort_plan &p, const uint32_t *keys, int shift, uint32_t *table,
-                       uint32_t *joint, const uint32_t *enable, hipStream_t s, bool zero_joint,
-                       uint32_t *rows, uint32_t *rows_cnt, uint32_t *done = nullptr, int shift2 = 0,
-                       Gate gate = Gate{}) {
+HistArgs hist_args(const rsort_plan &p, const uint32_t *keys, int shift, uint32_t *table) {
     HistArgs a{};
-    a.shift2 = (uint32_t)shift2;
-    a.mode = gate.mode;
-    a.mode_want = gate.want;
-    a.done = done;
-    a.rows = rows;
-    a.rows_cnt = rows_cnt;
     a.keys = keys;
     a.table = table;
     a.n = (uint64_t)p.n;
@@ -330,67 +285,48 @@ int do_histogram_joint(const rsort_plan &p, const uint32_t *keys, int shift, uin
     a.shift = (uint32_t)shift;
     a.vec = (((uintptr_t)keys & 15u) == 0) ? 1u : 0u;
     a.split = 1;
-    a.joint = joint;
-    a.joint_enable = enable;
-    PhaseScope ps(RSORT_PHASE_HISTOGRAM, p.n, s, gate);
-    // the first joint count of a sort clears the counts; a later one finds them cleared by the
-    // copy-mode histogram that used them (or, where that pass fell back, is disabled by `enable`)
-    // (the rows counter sits after the joint counts: cleared with them)
-    // (16 bytes past the counts, inside the 256-B-aligned region: a fill of a multiple of 16 bytes is one
-    // kernel, the 4-byte tail of an odd size was a second one, ~5 us per sort)
-    if (zero_joint && hipMemsetAsync(joint, 0, (size_t)kJointBins * kJointBins * 4 + 16, s) != hipSuccess)
-        return RSORT_ERR_HIP;
-    return hip_status(launch_histogram_joint(a, s));
+    return a;
 }
 
-// The next pass's chunks from the joint counts (rs_joint_bounds), after this pass's table is scanned
-// (ctab: a cut plan's pieces become row tasks where every chunk wrote its rows).
-int do_joint_bounds(const rsort_plan &p, const uint32_t *joint, const uint32_t *enable, uint32_t *bounds,
-                    uint32_t *plan, uint32_t *pcounts, const uint32_t *ctab, uint32_t *rows_cnt,
-                    const uint32_t *rowone, hipStream_t s, Gate gate = Gate{}) {
-    PhaseScope ps(RSORT_PHASE_HISTOGRAM, p.n, s, gate);
-    // a group may take one tile more than a fixed chunk; a cut-plan chunk boundary moves to a
-    // group boundary up to half a tile (and a quarter chunk) away
-    const uint32_t snap = (uint32_t)std::min<int64_t>(p.tile_keys / 2, p.n / (4 * (int64_t)kJointBins));
-    // the first cut plan of a sort (pass 1's, from pass 0's joint counts) balances estimated cost
-    // (rs_joint_bounds; RSORT_CUT_WEIGHTS=0 turns it off for A/B runs)
-    const uint32_t weighted = (enable == nullptr && cut_weights()) ? 1u : 0u;
-    return hip_status(launch_joint_bounds(joint, enable, bounds, plan, pcounts, (uint64_t)p.n,
-                                          (uint64_t)p.chunk_keys + (uint64_t)p.tile_keys, snap, weighted, s,
-                                          ctab, rows_cnt, rowone, gate.mode, gate.want));
+ScanArgs scan_args(const rsort_plan &p, uint32_t *table, uint32_t *bsums) {
+    ScanArgs a{};
+    a.table = table;
+    a.block_sums = bsums;
+    a.m = (uint64_t)p.table_entries;
+    a.nblocks = (uint32_t)p.scan_blocks;
+    return a;
 }
 
-int do_histogram(const rsort_plan &p, const uint32_t *keys, int shift, uint32_t *table,
-                 int dmode, const uint32_t *split, int nsplit, hipStream_t s,
-                 const uint32_t *bounds = nullptr, uint32_t *copy_src = nullptr,
-                 const uint32_t *plan = nullptr, uint32_t *pcounts = nullptr, uint32_t *zero = nullptr,
-                 uint32_t *done = nullptr, uint32_t *rows = nullptr, Gate gate = Gate{}) {
-    HistArgs a{};
-    a.mode = gate.mode;
-    a.mode_want = gate.want;
-    a.rows = rows;
-    a.zero = zero;
-    a.zero_n = zero ? (uint64_t)p.table_entries : 0u;
-    a.done = done;
-    a.bounds = bounds;
-    a.copy_src = copy_src;
-    a.plan = plan;
-    a.pcounts = pcounts;
-    a.keys = keys;
+ScatterArgs scatter_args(const rsort_plan &p, const PassIo &io, int shift, const uint32_t *table) {
+    ScatterArgs a{};
+    a.kin = io.kin;
+    a.vin = io.vin;
+    a.kout = io.kout;
+    a.vout = io.vout;
     a.table = table;
     a.n = (uint64_t)p.n;
     a.chunk_keys = (uint64_t)p.chunk_keys;
     a.num_chunks = (uint32_t)p.num_chunks;
     a.shift = (uint32_t)shift;
-    a.vec = (((uintptr_t)keys & 15u) == 0) ? 1u : 0u;
-    a.nsplit = (uint32_t)nsplit;
-    for (int i = 0; i < nsplit; ++i) a.splitters[i] = split[i];
+    a.rank_fault = g_rank_fault.load() ? 1u : 0u;
+    return a;
+}
+
+// a launch of a hybrid-eligible sort: works only while *g.mode == g.want (HistArgs::mode)
+template <class Args>
+Args gated(Args a, Gate g) {
+    a.mode = g.mode;
+    a.mode_want = g.want;
+    return a;
+}
+
+int run_histogram(const rsort_plan &p, HistArgs a, int dmode, hipStream_t s) {
+    if (a.zero) a.zero_n = (uint64_t)p.table_entries;
     // few, long chunks (one scatter workgroup per CU): several histogram workgroups per chunk,
     // their counts added into a zeroed table
     const int cus = device_cus();
     const int64_t want = 4 * (int64_t)(cus > 0 ? cus : 256);  // 1024-thread workgroups (hist_bits)
-    a.split = 1;
-    if (bounds != nullptr) {
+    if (a.bounds != nullptr) {
         // a digit-group pass (256 chunks of one workgroup each): copies the joint counts, counts the
         // cut plan's pieces, or counts one chunk per 1024-thread workgroup (as fast as split
         // workgroups, 0.62 ms per 2^30 keys, and no table memset launch)
@@ -398,74 +334,60 @@ int do_histogram(const rsort_plan &p, const uint32_t *keys, int shift, uint32_t 
     } else if (p.num_chunks < want && p.chunk_keys >= 8 * 4096) {
         a.split = (uint32_t)std::min<int64_t>({(want + p.num_chunks - 1) / p.num_chunks, p.chunk_keys / 4096, 64});
     }
-    PhaseScope ps(RSORT_PHASE_HISTOGRAM, p.n, s, gate);
-    if (a.split > 1 && hipMemsetAsync(table, 0, (size_t)p.table_entries * 4, s) != hipSuccess) return RSORT_ERR_HIP;
+    PhaseScope ps(RSORT_PHASE_HISTOGRAM, p.n, s, Gate{a.mode, a.mode_want});
+    if (a.split > 1 && hipMemsetAsync(a.table, 0, (size_t)p.table_entries * 4, s) != hipSuccess) return RSORT_ERR_HIP;
     return hip_status(launch_histogram(p.k_bits, dmode, a, s));
 }
 
-int do_scan(const rsort_plan &p, uint32_t *table, uint32_t *bsums, hipStream_t s, uint32_t *zero = nullptr,
-            uint32_t *done = nullptr, const Carve *cut = nullptr, const uint32_t *group_flag = nullptr,
-            Gate gate = Gate{}) {
-    ScanArgs a{};
-    a.mode = gate.mode;
-    a.mode_want = gate.want;
-    a.done = done;
-    if (cut != nullptr) {
-        // a digit-group pass: under a cut plan the scan assembles the table first
-        a.group_flag = group_flag;
-        a.joint = cut->joint;
-        a.plan = cut->plan;
-        a.pcounts = cut->pcounts;
-    }
-    a.table = table;
-    a.block_sums = bsums;
-    a.zero = zero;
-    a.zero_n = zero ? (uint64_t)p.table_entries : 0u;
-    a.m = (uint64_t)p.table_entries;
-    a.nblocks = (uint32_t)p.scan_blocks;
-    PhaseScope ps(RSORT_PHASE_SCAN, p.table_entries, s, gate);
+// Joint pass (pass p of a joint_plan counting for pass p + 1; a.joint set): one workgroup per chunk counts
+// this pass's table and the joint counts. a.joint_enable: nullptr, or the previous odd pass's mode: the joint count
+// runs after whole digit groups and after a cut plan (both leave the joint counts cleared: the copy-mode histogram,
+// the cut plan's scan), not after fixed chunks. After a cut plan the input is clustered: the joint count
+// adds runs of equal pairs once (rs_histogram's run path), so pass 3 gets its own cut plan too.
+int run_histogram_joint(const rsort_plan &p, const HistArgs &a, bool zero_joint, hipStream_t s) {
+    PhaseScope ps(RSORT_PHASE_HISTOGRAM, p.n, s, Gate{a.mode, a.mode_want});
+    // the first joint count of a sort clears the counts; a later one finds them cleared by the
+    // copy-mode histogram that used them (or, where that pass fell back, is disabled by joint_enable)
+    // (the rows counter sits after the joint counts: cleared with them)
+    // (16 bytes past the counts, inside the 256-B-aligned region: a fill of a multiple of 16 bytes is one
+    // kernel, the 4-byte tail of an odd size was a second one, ~5 us per sort)
+    if (zero_joint && hipMemsetAsync(a.joint, 0, (size_t)kJointBins * kJointBins * 4 + 16, s) != hipSuccess)
+        return RSORT_ERR_HIP;
+    return hip_status(launch_histogram_joint(a, s));
+}
+
+// The next pass's chunks from the joint counts (rs_joint_bounds), after this pass's table is scanned
+// (a.ctab: a cut plan's pieces become row tasks where every chunk wrote its rows).
+int run_joint_bounds(const rsort_plan &p, JointBoundsArgs a, hipStream_t s) {
+    a.n = (uint64_t)p.n;
+    // a group may take one tile more than a fixed chunk; a cut-plan chunk boundary moves to a
+    // group boundary up to half a tile (and a quarter chunk) away
+    a.max_keys = (uint64_t)p.chunk_keys + (uint64_t)p.tile_keys;
+    a.snap = (uint32_t)std::min<int64_t>(p.tile_keys / 2, p.n / (4 * (int64_t)kJointBins));
+    // the first cut plan of a sort (pass 1's, from pass 0's joint counts) balances estimated cost
+    // (rs_joint_bounds; RSORT_CUT_WEIGHTS=0 turns it off for A/B runs)
+    a.weighted = (a.enable == nullptr && lab().cut_weights) ? 1u : 0u;
+    PhaseScope ps(RSORT_PHASE_HISTOGRAM, p.n, s, Gate{a.mode, a.mode_want});
+    return hip_status(launch_joint_bounds(a, s));
+}
+
+int run_scan(const rsort_plan &p, ScanArgs a, hipStream_t s) {
+    if (a.zero) a.zero_n = (uint64_t)p.table_entries;
+    PhaseScope ps(RSORT_PHASE_SCAN, p.table_entries, s, Gate{a.mode, a.mode_want});
     return hip_status(launch_scan(a, s));
 }
 
-int do_scatter(const rsort_plan &p, const uint32_t *kin, const uint32_t *vin, uint32_t *kout,
-               uint32_t *vout, int shift, const uint32_t *table, int local_only, int dmode,
-               const uint32_t *split, int nsplit, hipStream_t s, const uint32_t *bounds = nullptr,
-               uint32_t *next_table = nullptr, uint32_t *tail_zero = nullptr, uint32_t *done = nullptr,
-               const uint32_t *cl_select = nullptr, int raw_table = 0, uint32_t *zero_table = nullptr,
-               uint32_t *check = nullptr, Gate gate = Gate{}) {
-    ScatterArgs a{};
-    a.mode = gate.mode;
-    a.mode_want = gate.want;
-    a.check = check;
-    a.rank_fault = g_rank_fault.load() ? 1u : 0u;
-    a.raw_table = raw_table ? 1u : 0u;
-    a.zero_table = zero_table;
-    a.cl_select = cl_select;
-    a.bounds = bounds;
-    a.next_table = next_table;
-    a.tail_zero = tail_zero;
-    a.done = done;
-    a.kin = kin;
-    a.vin = vin;
-    a.kout = kout;
-    a.vout = vout;
-    a.table = table;
-    a.n = (uint64_t)p.n;
-    a.chunk_keys = (uint64_t)p.chunk_keys;
-    a.num_chunks = (uint32_t)p.num_chunks;
-    a.shift = (uint32_t)shift;
-    a.local_only = local_only ? 1u : 0u;
-    a.nsplit = (uint32_t)nsplit;
-    for (int i = 0; i < nsplit; ++i) a.splitters[i] = split[i];
+int run_scatter(const rsort_plan &p, const ScatterArgs &a, int dmode, hipStream_t s) {
     const int rank = internal_rank((dmode == kDigitShift) ? g_rank_algo.load() : RSORT_RANK_MATCH);
     const int geom = geom_from_shape(p.threads, p.tile_keys, p.pairs);
     if (!scatter_available(p.k_bits, p.pairs, rank, dmode, geom)) return RSORT_ERR_ARG;
-    const int aligned16 = line_capable(kout, vout, p.pairs, p.n);
-    if ((bounds || next_table || raw_table) && !(rank == kRankAtomic && aligned16 && !local_only && dmode == kDigitShift))
+    const int aligned16 = line_capable(a.kout, a.vout, p.pairs, p.n);
+    if ((a.bounds || a.next_table || a.raw_table) &&
+        !(rank == kRankAtomic && aligned16 && !a.local_only && dmode == kDigitShift))
         return RSORT_ERR_ARG;  // group chunks, next-digit counts, raw tables: rs_scatter_lines only
     // a multi-GPU partition's scatter (splitter digits) is recorded apart from the sort's passes
-    PhaseScope ps(dmode == kDigitSplit ? RSORT_PHASE_PARTITION : RSORT_PHASE_SCATTER, p.n, s, gate);
-    return hip_status(launch_scatter(p.k_bits, p.pairs, rank, dmode, geom, local_only ? 0 : aligned16, a, s));
+    PhaseScope ps(dmode == kDigitSplit ? RSORT_PHASE_PARTITION : RSORT_PHASE_SCATTER, p.n, s, Gate{a.mode, a.mode_want});
+    return hip_status(launch_scatter(p.k_bits, p.pairs, rank, dmode, geom, a.local_only ? 0 : aligned16, a, s));
 }
 
 int check_plan(const rsort_plan *p) {
@@ -491,11 +413,7 @@ int check_plan(const rsort_plan *p) {
 constexpr int64_t kHybMinKeys = (int64_t)1 << 28;
 constexpr int64_t kHybMaxKeys = (int64_t)kHybCapacity * kHybBuckets;
 int64_t hyb_min_keys() {
-    static const int64_t v = [] {
-        const char *e = lab_env("RSORT_HYB_MIN_KEYS");
-        const long long x = e ? atoll(e) : 0;
-        return (x >= 1 && x < ((long long)1 << 32)) ? (int64_t)x : kHybMinKeys;
-    }();
+    static const int64_t v = lab_int("RSORT_HYB_MIN_KEYS", 1, ((long long)1 << 32) - 1, kHybMinKeys);
     return v;
 }
 
@@ -504,14 +422,6 @@ int64_t hyb_min_keys() {
 // bench runs: 6.52 ms with 1, 6.41 with 2, 6.33 with 4, 6.28 with 8 and with 16, 6.40 with 32 (DESIGN §3 "Hybrid
 // route"; RSORT_HYB_GRID_MULT under RSORT_LAB=1 for A/B runs).
 constexpr int kHybGridMult = 8;
-int hyb_grid_mult() {
-    static const int v = [] {
-        const char *e = lab_env("RSORT_HYB_GRID_MULT");
-        const int x = e ? atoi(e) : 0;
-        return (x >= 1 && x <= 256) ? x : kHybGridMult;
-    }();
-    return v;
-}
 
 // The sample gate's threshold. Each of the gate's kHybGateGroups workgroups reads m = min(n, kHybSample) /
 // kHybGateGroups keys at a fixed stride over its part of the input and counts them by their top 16 bits. A bucket
@@ -548,6 +458,209 @@ bool hybrid_eligible(const rsort_plan &p, bool joint, bool inplace, bool allow) 
     return p.n >= hyb_min_keys() && p.n <= kHybMaxKeys;
 }
 
+// What the pass loops of one sort share. Every LSD launch carries the gate `lsd` ({}: not hybrid-eligible) and
+// every scatter the check word; pass i reads (sk, sv) and the last pass lands in (kout, vout).
+struct SortCtx {
+    const rsort_plan &p;
+    const Carve c;
+    hipStream_t s;
+    Gate lsd;
+    const uint32_t *sk, *sv;
+    uint32_t *kout, *vout;
+
+    HistArgs hist(int i, uint32_t *table) const { return gated(hist_args(p, sk, i * p.k_bits, table), lsd); }
+    ScanArgs scan(uint32_t *table) const { return gated(scan_args(p, table, c.bsums), lsd); }
+    ScatterArgs scatter(int i, const uint32_t *table) const {
+        const bool to_out = ((p.passes - 1 - i) % 2) == 0;
+        const PassIo io{sk, sv, to_out ? kout : c.tmp_k, to_out ? vout : c.tmp_v};
+        ScatterArgs a = gated(scatter_args(p, io, i * p.k_bits, table), lsd);
+        a.check = c.done + kDoneErr;
+        return a;
+    }
+    // runs a pass's scatter; what it wrote is the next pass's input
+    int run_pass(const ScatterArgs &a) {
+        const int st = run_scatter(p, a, kDigitShift, s);
+        sk = a.kout;
+        sv = a.vout;
+        return st;
+    }
+    int hybrid_prologue();
+    int plain_passes();
+    int group_passes(bool hyb);
+    int next_digit_passes(bool rawt);
+};
+
+// Hybrid route (not in place: sk is the sort's input): gate, joint count of (digit 3, digit 2), mode + bucket
+// starts, pass A in -> out, pass B out -> tmp, bucket phase tmp -> out; then the LSD passes (gated by `lsd` from
+// here on), which run when the mode word says so. Every kernel of the unselected route leaves at once.
+int SortCtx::hybrid_prologue() {
+    int st;
+    const bool force = g_hybrid.load() == RSORT_HYBRID_FORCE;
+    const Gate run{c.done + kHybMode, kHybRun};
+    lsd = Gate{c.done + kHybMode, kHybLsd};
+    uint32_t *hb = c.plan;  // pass B's chunks (the cut-plan area: the LSD passes use it only when they run)
+    HybArgs h{};
+    h.kin = sk;
+    h.kout = kout;
+    h.joint = c.joint;
+    h.bounds = hb;
+    h.gflags = c.bounds;
+    h.done = c.done;
+    h.n = (uint64_t)p.n;
+    h.threshold = gate_threshold(p.n);
+    h.force = force ? 1u : 0u;
+    h.rank_fault = g_rank_fault.load() ? 1u : 0u;
+    hyb_note_bucket();
+    {
+        // the one clear of the joint counts, with the rows counter and the gate's flag behind them: the LSD
+        // passes find them cleared -- never counted after a skewed verdict, cleared again by rs_hyb_bounds
+        // after an overflow
+        PhaseScope ps(RSORT_PHASE_HISTOGRAM, std::min<int64_t>(p.n, kHybSample), s);
+        if (hipMemsetAsync(c.joint, 0, (size_t)kJointBins * kJointBins * 4 + 16, s) != hipSuccess) return RSORT_ERR_HIP;
+        if ((st = hip_status(launch_hyb_gate(h, s)))) return st;
+    }
+    // the joint count runs when the gate's flag stayed 0 (FORCE: always)
+    HistArgs jc = gated(hist_args(p, sk, 24, c.table), force ? Gate{} : Gate{c.joint + kHybGateFlag, 0u});
+    jc.joint = c.joint;
+    jc.shift2 = 16;
+    if ((st = run_histogram_joint(p, jc, false, s))) return st;
+    {
+        PhaseScope ps(RSORT_PHASE_HISTOGRAM, p.n, s);
+        if ((st = hip_status(launch_hyb_bounds(h, s)))) return st;
+    }
+    if ((st = run_scan(p, gated(scan_args(p, c.table, c.bsums), run), s))) return st;
+    ScatterArgs pa = gated(scatter_args(p, PassIo{sk, nullptr, kout, nullptr}, 24, c.table), run);
+    pa.check = c.done + kDoneErr;
+    if ((st = run_scatter(p, pa, kDigitShift, s))) return st;
+    ScatterArgs pb = gated(scatter_args(p, PassIo{kout, nullptr, c.tmp_k, nullptr}, 16, c.joint), run);
+    pb.bounds = hb;
+    pb.check = c.done + kDoneErr;
+    if ((st = run_scatter(p, pb, kDigitShift, s))) return st;
+    const int cus = std::max(1, device_cus());
+    const int bpc = std::max(1, hyb_blocks_per_cu());
+    static const int mult = (int)lab_int("RSORT_HYB_GRID_MULT", 1, 256, kHybGridMult);
+    const uint32_t grid = (uint32_t)std::min<int64_t>(kHybBuckets, (int64_t)cus * bpc * mult);
+    h.kin = c.tmp_k;
+    PhaseScope ps(RSORT_PHASE_SCATTER, p.n, s, run);
+    return hip_status(launch_hyb_bucket(h, grid, s));
+}
+
+// Plain LSD passes: histogram, scan, scatter.
+int SortCtx::plain_passes() {
+    int st;
+    for (int i = 0; i < p.passes; ++i) {
+        HistArgs h = hist(i, c.table);
+        if (i == 0) h.done = c.done;  // pass 0's histogram clears the check words (rsort_plan_check: a clean record)
+        if ((st = run_histogram(p, h, kDigitShift, s))) return st;
+        if ((st = run_scan(p, scan(c.table), s))) return st;
+        if ((st = run_pass(scatter(i, c.table)))) return st;
+    }
+    return RSORT_OK;
+}
+
+// Digit-group chunks (joint_plan: k = 8, four passes): two pairs of passes. The even pass of a pair counts, with
+// its own table, the joint counts of (its digit, the next); rs_joint_bounds makes the odd pass's chunks of them
+// (`bounds`: whole digit groups or a cut plan), and the odd pass then reads no keys for its histogram.
+// hyb: the hybrid prologue ran (it cleared the check words and the joint counts).
+int SortCtx::group_passes(bool hyb) {
+    uint32_t *const rows = lab().piece_rows ? c.rows : nullptr, *const rows_cnt = rows ? c.rows_cnt : nullptr;
+    int st;
+    for (int g = 0; g < p.passes / 2; ++g) {
+        uint32_t *const bounds = c.bounds + g * kBoundsWords;                    // this pair's chunks
+        const uint32_t *const prev = g > 0 ? bounds - kBoundsWords : nullptr;    // the pair's before
+        int i = 2 * g;
+        // even pass: the joint count (after a pair that fell back to fixed chunks: off), the table's scan, the
+        // next pass's chunks (after the scan: a cut plan finds the previous chunks' positions in it)
+        HistArgs jc = hist(i, c.table);
+        jc.joint = c.joint;
+        jc.joint_enable = prev;
+        jc.rows = rows;
+        jc.rows_cnt = rows_cnt;
+        if (i == 0 && !hyb) jc.done = c.done;  // pass 0's histogram clears the check words
+        if ((st = run_histogram_joint(p, jc, /*zero_joint=*/i == 0 && !hyb, s))) return st;
+        if ((st = run_scan(p, scan(c.table), s))) return st;
+        JointBoundsArgs jb = gated(JointBoundsArgs{}, lsd);
+        jb.joint = c.joint;
+        jb.enable = prev;
+        jb.bounds = bounds;
+        jb.plan = c.plan;
+        jb.pcounts = c.pcounts;
+        jb.ctab = c.table;
+        jb.rows_cnt = rows_cnt;
+        jb.rowone = rows ? rows + kRowsWords : nullptr;
+        if ((st = run_joint_bounds(p, jb, s))) return st;
+        // passes after the first: where the previous odd pass's groups were unbalanced (skewed, duplicate-heavy
+        // keys: runs of equal keys in this pass's input), the clustered-input kernel runs (rank_add_hot), else
+        // the plain one -- chosen on the device
+        ScatterArgs even = scatter(i, c.table);
+        even.cl_select = prev;
+        if ((st = run_pass(even))) return st;
+
+        // odd pass: the table is the joint counts (copied), or assembled by the scan from the cut plan's pieces
+        i = 2 * g + 1;
+        HistArgs h = hist(i, c.table);
+        h.bounds = bounds;
+        h.copy_src = c.joint;
+        h.plan = c.plan;
+        h.pcounts = c.pcounts;
+        h.rows = rows;
+        if ((st = run_histogram(p, h, kDigitShift, s))) return st;
+        ScanArgs sc = scan(c.table);
+        sc.group_flag = bounds;
+        sc.joint = c.joint;
+        sc.plan = c.plan;
+        sc.pcounts = c.pcounts;
+        if ((st = run_scan(p, sc, s))) return st;
+        ScatterArgs odd = scatter(i, c.table);
+        odd.bounds = bounds;
+        odd.cl_select = bounds;
+        if ((st = run_pass(odd))) return st;
+    }
+    return RSORT_OK;
+}
+
+// Next-digit counts (next_plan: k = 3, 4 keys): only pass 0 reads keys for a histogram; every pass adds the next
+// pass's table from where it writes each key. Pass i reads `tab` and adds into `nxt`. Tail scans alternate two
+// tables: the workgroup of pass i that finishes last scans nxt and clears tab. Raw tables (rawt) rotate three: every
+// workgroup of a pass derives its offsets from the raw counts, and clears its part of `clr` for the pass after next.
+int SortCtx::next_digit_passes(bool rawt) {
+    const int P = p.passes, tables = rawt ? 3 : 2;
+    uint32_t *const rot[3] = {c.table, c.table2, c.table3};
+    int st;
+    for (int i = 0; i < P; ++i) {
+        uint32_t *const tab = rot[i % tables];
+        uint32_t *const nxt = i + 1 < P ? rot[(i + 1) % tables] : nullptr;
+        uint32_t *const clr = (rawt && i + 2 < P) ? rot[(i + 2) % tables] : nullptr;
+        if (i == 0) {
+            // pass 0's table is counted from the keys (its histogram clears the check words and, raw tables, nxt)
+            // and, tail scans, scanned by launches, which also clear nxt and arm the tail counter
+            HistArgs h = hist(0, tab);
+            h.done = c.done;
+            if (rawt) h.zero = nxt;
+            if ((st = run_histogram(p, h, kDigitShift, s))) return st;
+            if (!rawt) {
+                ScanArgs sc = scan(tab);
+                sc.zero = nxt;
+                sc.done = c.done;
+                if ((st = run_scan(p, sc, s))) return st;
+            }
+        }
+        ScatterArgs a = scatter(i, tab);
+        a.next_table = nxt;
+        a.raw_table = rawt ? 1u : 0u;
+        a.zero_table = clr;
+        if (nxt && !rawt) a.tail_zero = tab;
+        if (nxt || rawt) a.done = c.done;
+        if ((st = run_pass(a))) return st;
+        // test hook: corrupt the raw table pass 1 reads (its total is then not n: every pass-1 workgroup
+        // writes nothing and records the failure for rsort_plan_check / RSORT_ERR_CHECK)
+        if (i == 0 && rawt && nxt && g_table_fault.load() &&
+            hipMemsetD32Async((hipDeviceptr_t)nxt, 0xFFFFFFFFu, 1, s) != hipSuccess)
+            return RSORT_ERR_HIP;
+    }
+    return RSORT_OK;
+}
+
 int sort_planned(const rsort_plan &p, const uint32_t *kin, const uint32_t *vin, uint32_t *kout,
                  uint32_t *vout, void *ws, size_t wsb, hipStream_t s, bool allow_hybrid = true) {
     int st = check_plan(&p);
@@ -557,11 +670,10 @@ int sort_planned(const rsort_plan &p, const uint32_t *kin, const uint32_t *vin, 
     if (!aligned4(kin) || !aligned4(kout) || (p.pairs && (!aligned4(vin) || !aligned4(vout))))
         return RSORT_ERR_ALIGN;
     if (wsb < p.workspace_bytes) return RSORT_ERR_WORKSPACE;
-    const Carve c = carve(p, ws);
-    const int P = p.passes;
-    const uint32_t *sk = kin, *sv = vin;
+    SortCtx x{p, carve(p, ws), s, Gate{}, kin, vin, kout, vout};
+    const Carve &c = x.c;
     const bool inplace = (kin == kout) || (p.pairs && vin == vout);
-    if (inplace && (P % 2 == 1)) {
+    if (inplace && (p.passes % 2 == 1)) {
         // pass 0 must not read the buffer it writes: stage the input in the ping-pong buffer
         PhaseScope ps(RSORT_PHASE_COPY, p.n, s);
         if (hipMemcpyAsync(c.tmp_k, kin, (size_t)p.n * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
@@ -569,11 +681,11 @@ int sort_planned(const rsort_plan &p, const uint32_t *kin, const uint32_t *vin, 
         if (p.pairs &&
             hipMemcpyAsync(c.tmp_v, vin, (size_t)p.n * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
             return RSORT_ERR_HIP;
-        sk = c.tmp_k;
-        sv = c.tmp_v;
+        x.sk = c.tmp_k;
+        x.sv = c.tmp_v;
     }
-    // digit-group chunks on every second pass (joint_plan): needs rs_scatter_lines for both
-    // outputs (lane-ordered ranks, 16-B aligned ping-pong buffers)
+    // The routes, one per sort (joint needs k = 8, nextc k = 3 or 4). Digit-group chunks on every second pass
+    // (joint_plan): needs rs_scatter_lines for both outputs (lane-ordered ranks, 16-B aligned ping-pong buffers)
     const bool joint = joint_plan(p) && g_group_chunks.load() != 0 &&
                        internal_rank(g_rank_algo.load()) == kRankAtomic && line_capable(kout, vout, p.pairs, p.n) &&
                        line_capable(c.tmp_k, c.tmp_v, p.pairs, p.n);
@@ -584,120 +696,12 @@ int sort_planned(const rsort_plan &p, const uint32_t *kin, const uint32_t *vin, 
     const bool nextc = next_plan(p) && g_group_chunks.load() != 0 && internal_rank(g_rank_algo.load()) == kRankAtomic &&
                        line_capable(kout, nullptr, 0, p.n) && line_capable(c.tmp_k, nullptr, 0, p.n);
     // next-digit plans: every pass after the first derives its offsets from the raw counts the pass
-    // before added (three tables in rotation: read / added into / cleared for the pass after next),
-    // instead of the last workgroup of each pass scanning them (RSORT_NX_TAIL=1: that older way)
+    // before added, instead of the last workgroup of each pass scanning them (RSORT_NX_TAIL=1: that older way)
     // (raw tables only up to kRawTableMaxChunks chunks: each workgroup reads the whole table)
-    const bool rawt = nextc && !nx_tail() && p.num_chunks <= kRawTableMaxChunks;
-    uint32_t *const rot[3] = {c.table, c.table2, c.table3};
-    uint32_t *const rows = piece_rows() ? c.rows : nullptr, *const rows_cnt = rows ? c.rows_cnt : nullptr;
-    // Hybrid route: gate, joint count of (digit 3, digit 2), mode + bucket starts, pass A in -> out, pass B
-    // out -> tmp, bucket phase tmp -> out; then the LSD passes below, which run when the mode word says so.
-    // Every kernel of the unselected route leaves at once.
+    const bool rawt = nextc && !lab().nx_tail && p.num_chunks <= kRawTableMaxChunks;
     const bool hyb = hybrid_eligible(p, joint, inplace || kin == c.tmp_k, allow_hybrid);
-    Gate lsd{};
-    if (hyb) {
-        const uint32_t *mode = c.done + kHybMode;
-        const bool force = g_hybrid.load() == RSORT_HYBRID_FORCE;
-        // the joint count runs when the gate's flag stayed 0 (FORCE: always)
-        const Gate g_try = force ? Gate{} : Gate{c.joint + kHybGateFlag, 0u}, g_run{mode, kHybRun};
-        lsd = Gate{mode, kHybLsd};
-        uint32_t *hb = c.plan;  // pass B's chunks (the cut-plan area: the LSD passes use it only when they run)
-        HybArgs h{};
-        h.kin = kin;
-        h.kout = kout;
-        h.joint = c.joint;
-        h.bounds = hb;
-        h.gflags = c.bounds;
-        h.done = c.done;
-        h.n = (uint64_t)p.n;
-        h.threshold = gate_threshold(p.n);
-        h.force = force ? 1u : 0u;
-        h.rank_fault = g_rank_fault.load() ? 1u : 0u;
-        hyb_note_bucket();
-        {
-            // the one clear of the joint counts, with the rows counter and the gate's flag behind them: the LSD
-            // passes find them cleared -- never counted after a skewed verdict, cleared again by rs_hyb_bounds
-            // after an overflow
-            PhaseScope ps(RSORT_PHASE_HISTOGRAM, std::min<int64_t>(p.n, kHybSample), s);
-            if (hipMemsetAsync(c.joint, 0, (size_t)kJointBins * kJointBins * 4 + 16, s) != hipSuccess) return RSORT_ERR_HIP;
-            if ((st = hip_status(launch_hyb_gate(h, s)))) return st;
-        }
-        if ((st = do_histogram_joint(p, kin, 24, c.table, c.joint, nullptr, s, false, nullptr, nullptr, nullptr, 16,
-                                     g_try)))
-            return st;
-        {
-            PhaseScope ps(RSORT_PHASE_HISTOGRAM, p.n, s);
-            if ((st = hip_status(launch_hyb_bounds(h, s)))) return st;
-        }
-        if ((st = do_scan(p, c.table, c.bsums, s, nullptr, nullptr, nullptr, nullptr, g_run))) return st;
-        if ((st = do_scatter(p, kin, nullptr, kout, nullptr, 24, c.table, 0, kDigitShift, nullptr, 0, s, nullptr,
-                             nullptr, nullptr, nullptr, nullptr, 0, nullptr, c.done + kDoneErr, g_run)))
-            return st;
-        if ((st = do_scatter(p, kout, nullptr, c.tmp_k, nullptr, 16, c.joint, 0, kDigitShift, nullptr, 0, s, hb,
-                             nullptr, nullptr, nullptr, nullptr, 0, nullptr, c.done + kDoneErr, g_run)))
-            return st;
-        {
-            const int cus = std::max(1, device_cus());
-            const int bpc = std::max(1, hyb_blocks_per_cu());
-            const uint32_t grid = (uint32_t)std::min<int64_t>(kHybBuckets, (int64_t)cus * bpc * hyb_grid_mult());
-            h.kin = c.tmp_k;
-            PhaseScope ps(RSORT_PHASE_SCATTER, p.n, s, g_run);
-            if ((st = hip_status(launch_hyb_bucket(h, grid, s)))) return st;
-        }
-    }
-    for (int i = 0; i < P; ++i) {
-        const int shift = i * p.k_bits;
-        const bool to_out = ((P - 1 - i) % 2) == 0;  // the last pass always lands in `out`
-        uint32_t *dk = to_out ? kout : c.tmp_k;
-        uint32_t *dv = to_out ? vout : c.tmp_v;
-        // even pass i counts the joint counts for pass i + 1; odd pass i may use them
-        const bool count_joint = joint && (i % 2 == 0) && i + 1 < P;
-        const uint32_t *bounds = (joint && (i % 2 == 1)) ? c.bounds + (i / 2) * kBoundsWords : nullptr;
-        // next-digit plans alternate two tables (tail scans) or rotate three (raw tables): pass i
-        // reads tab, adds pass i + 1's into nxt
-        uint32_t *tab = rawt ? rot[i % 3] : (nextc && (i % 2 == 1)) ? c.table2 : c.table;
-        uint32_t *nxt = (nextc && i + 1 < P) ? (rawt ? rot[(i + 1) % 3] : (i % 2 == 1) ? c.table : c.table2) : nullptr;
-        uint32_t *clr = (rawt && i + 2 < P) ? rot[(i + 2) % 3] : nullptr;  // for the pass after next
-        const uint32_t *enable = (count_joint && i >= 2) ? c.bounds + (i / 2 - 1) * kBoundsWords : nullptr;
-        // pass 0's histogram clears the check words (rsort_plan_check: a clean record for this sort)
-        if (count_joint) {
-            // (a hybrid-eligible sort: the gate cleared the check words, the hybrid launches the joint counts)
-            if ((st = do_histogram_joint(p, sk, shift, c.table, c.joint, enable, s, i == 0 && !hyb, rows, rows_cnt,
-                                         (i == 0 && !hyb) ? c.done : nullptr, 0, lsd)))
-                return st;
-        } else if (!(nextc && i > 0) &&
-                   (st = do_histogram(p, sk, shift, tab, kDigitShift, nullptr, 0, s, bounds, c.joint, c.plan,
-                                      c.pcounts, rawt ? nxt : nullptr, i == 0 ? c.done : nullptr,
-                                      bounds ? rows : nullptr, lsd))) {
-            return st;
-        }
-        // next-digit plans: pass 0's table is scanned by launches (which also arm the tail counter;
-        // raw tables: no scan at all, the histogram cleared the next table), every later table by the
-        // previous scatter's last workgroup (raw tables: by every workgroup of the pass itself)
-        if (!(nextc && i > 0) && !rawt &&
-            (st = do_scan(p, tab, c.bsums, s, nxt, nextc ? c.done : nullptr, bounds ? &c : nullptr, bounds, lsd)))
-            return st;
-        // the next pass's chunks (after the scan: a cut plan finds the previous chunks' positions in it)
-        if (count_joint && (st = do_joint_bounds(p, c.joint, enable, c.bounds + (i / 2) * kBoundsWords, c.plan,
-                                                 c.pcounts, tab, rows_cnt, rows ? rows + kRowsWords : nullptr, s, lsd)))
-            return st;
-        // passes after the first of a digit-group sort: where the previous odd pass's groups were
-        // unbalanced (skewed, duplicate-heavy keys: runs of equal keys in this pass's input), the
-        // clustered-input kernel runs (rank_add_hot), else the plain one -- chosen on the device
-        const uint32_t *cl = (joint && i >= 1) ? c.bounds + ((i - 1) / 2) * kBoundsWords : nullptr;
-        if ((st = do_scatter(p, sk, sv, dk, dv, shift, tab, 0, kDigitShift, nullptr, 0, s, bounds, nxt,
-                             (nxt && !rawt) ? tab : nullptr, (nextc && (nxt || rawt)) ? c.done : nullptr, cl,
-                             rawt, clr, c.done + kDoneErr, lsd)))
-            return st;
-        // test hook: corrupt the raw table pass 1 reads (its total is then not n: every pass-1 workgroup
-        // writes nothing and records the failure for rsort_plan_check / RSORT_ERR_CHECK)
-        if (i == 0 && rawt && nxt && g_table_fault.load() &&
-            hipMemsetD32Async((hipDeviceptr_t)nxt, 0xFFFFFFFFu, 1, s) != hipSuccess)
-            return RSORT_ERR_HIP;
-        sk = dk;
-        sv = dv;
-    }
-    return RSORT_OK;
+    if (hyb && (st = x.hybrid_prologue())) return st;
+    return joint ? x.group_passes(hyb) : nextc ? x.next_digit_passes(rawt) : x.plain_passes();
 }
 
 // ------------------------------------------------------------------------------ host entry cache
@@ -707,6 +711,18 @@ struct DevCache {
     void *buf = nullptr;
     size_t cap = 0;
     hipStream_t stream = nullptr;
+
+    // (under mu) makes the stream and grows the buffer to at least `need` bytes
+    int reserve(size_t need) {
+        if (!stream && hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) return RSORT_ERR_HIP;
+        if (cap >= need) return RSORT_OK;
+        if (buf) (void)hipFree(buf);
+        buf = nullptr;
+        cap = 0;
+        if (hipMalloc(&buf, need) != hipSuccess) return RSORT_ERR_ALLOC;
+        cap = need;
+        return RSORT_OK;
+    }
 };
 std::mutex g_cache_mu;
 std::vector<DevCache *> g_caches;
@@ -738,16 +754,7 @@ int host_sort(const uint32_t *kin, const uint32_t *vin, uint32_t *kout, uint32_t
     DevCache *dc = cache_for(dev);
     std::lock_guard<std::mutex> g(dc->mu);
     const size_t nb = align256((size_t)n * 4);
-    const size_t need = nb * (pairs ? 4 : 2) + p.workspace_bytes;
-    if (!dc->stream && hipStreamCreateWithFlags(&dc->stream, hipStreamNonBlocking) != hipSuccess)
-        return RSORT_ERR_HIP;
-    if (dc->cap < need) {
-        if (dc->buf) (void)hipFree(dc->buf);
-        dc->buf = nullptr;
-        dc->cap = 0;
-        if (hipMalloc(&dc->buf, need) != hipSuccess) return RSORT_ERR_ALLOC;
-        dc->cap = need;
-    }
+    if ((st = dc->reserve(nb * (pairs ? 4 : 2) + p.workspace_bytes))) return st;
     char *q = (char *)dc->buf;
     uint32_t *d_kin = (uint32_t *)q;
     uint32_t *d_kout = (uint32_t *)(q + nb);
@@ -775,9 +782,7 @@ int host_sort(const uint32_t *kin, const uint32_t *vin, uint32_t *kout, uint32_t
         return RSORT_ERR_HIP;
     // this entry waits for the device anyway: the sort's self-checks (rsort_plan_check) are read here
     uint32_t check = 0;
-    if (hipMemcpyAsync(&check, carve(p, ws).done + kDoneErr, 4, hipMemcpyDeviceToHost, s) != hipSuccess)
-        return RSORT_ERR_HIP;
-    if (hipStreamSynchronize(s) != hipSuccess) return RSORT_ERR_HIP;
+    if ((st = read_words(&check, carve(p, ws).done + kDoneErr, 1, s))) return st;
     return check ? RSORT_ERR_CHECK : RSORT_OK;
 }
 
@@ -889,16 +894,7 @@ int seg_host_sort(const uint32_t *kin, const uint32_t *vin, uint32_t *kout, uint
     std::lock_guard<std::mutex> g(dc->mu);
     const size_t nb = align256((size_t)n * 4), ob = align256((size_t)(nseg + 1) * 4);
     const size_t wsb = seg_carve(n, nseg, pairs, nullptr).bytes;
-    const size_t need = nb * (pairs ? 4 : 2) + ob + wsb;
-    if (!dc->stream && hipStreamCreateWithFlags(&dc->stream, hipStreamNonBlocking) != hipSuccess)
-        return RSORT_ERR_HIP;
-    if (dc->cap < need) {
-        if (dc->buf) (void)hipFree(dc->buf);
-        dc->buf = nullptr;
-        dc->cap = 0;
-        if (hipMalloc(&dc->buf, need) != hipSuccess) return RSORT_ERR_ALLOC;
-        dc->cap = need;
-    }
+    if ((st = dc->reserve(nb * (pairs ? 4 : 2) + ob + wsb))) return st;
     char *q = (char *)dc->buf;
     uint32_t *d_kin = (uint32_t *)q;
     uint32_t *d_kout = (uint32_t *)(q + nb);
@@ -921,10 +917,7 @@ int seg_host_sort(const uint32_t *kin, const uint32_t *vin, uint32_t *kout, uint
     if (pairs && hipMemcpyAsync(vout + lo, d_vout + lo, m * 4, hipMemcpyDeviceToHost, s) != hipSuccess)
         return RSORT_ERR_HIP;
     uint32_t check = 0;
-    if (hipMemcpyAsync(&check, seg_carve(n, nseg, pairs, ws).counters + kSegCheckWord, 4, hipMemcpyDeviceToHost, s) !=
-        hipSuccess)
-        return RSORT_ERR_HIP;
-    if (hipStreamSynchronize(s) != hipSuccess) return RSORT_ERR_HIP;
+    if ((st = read_words(&check, seg_carve(n, nseg, pairs, ws).counters + kSegCheckWord, 1, s))) return st;
     return check ? RSORT_ERR_CHECK : RSORT_OK;
 }
 
@@ -968,9 +961,7 @@ size_t rsort_workspace_size(int64_t n, int k_bits, int pairs) {
 int rsort_sort_planned(const rsort_plan *plan, const uint32_t *d_keys_in, const uint32_t *d_vals_in,
                        uint32_t *d_keys_out, uint32_t *d_vals_out, void *d_workspace,
                        size_t workspace_bytes, void *stream) {
-    if (!plan) return RSORT_ERR_ARG;
-    return sort_planned(*plan, d_keys_in, d_vals_in, d_keys_out, d_vals_out, d_workspace,
-                        workspace_bytes, (hipStream_t)stream);
+    return rsort_sort_planned_ex(plan, d_keys_in, d_vals_in, d_keys_out, d_vals_out, d_workspace, workspace_bytes, stream, 0);
 }
 
 int rsort_sort_planned_ex(const rsort_plan *plan, const uint32_t *d_keys_in, const uint32_t *d_vals_in,
@@ -1047,10 +1038,8 @@ int rsort_segmented_check(int64_t n, int64_t num_segments, int pairs, const void
     if (n == 0 || num_segments == 0) return RSORT_OK;
     if (!d_workspace) return RSORT_ERR_ARG;
     const SegCarve c = seg_carve(n, num_segments, pairs ? 1 : 0, const_cast<void *>(d_workspace));
-    hipStream_t s = (hipStream_t)stream;
     uint32_t h[kSegCheckWord + 1] = {0};
-    if (hipMemcpyAsync(h, c.counters, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess) return RSORT_ERR_HIP;
-    if (hipStreamSynchronize(s) != hipSuccess) return RSORT_ERR_HIP;
+    if ((st = read_words(h, c.counters, kSegCheckWord + 1, (hipStream_t)stream))) return st;
     *flags = (int)(h[kSegCheckWord] & (kCheckRankOrder | kCheckOffsets));
     if (class_counts) {  // (one wave or one small workgroup per segment: both are the small class)
         class_counts[0] = (int64_t)h[kSegWave] + (int64_t)h[kSegSmall];
@@ -1073,7 +1062,7 @@ int rsort_pass_histogram(const rsort_plan *plan, const uint32_t *d_keys, int shi
     if (shift < 0 || shift > 31) return RSORT_ERR_ARG;
     if (plan->n == 0) return RSORT_OK;
     if (!d_keys || !d_table) return RSORT_ERR_ARG;
-    return do_histogram(*plan, d_keys, shift, d_table, kDigitShift, nullptr, 0, (hipStream_t)stream);
+    return run_histogram(*plan, hist_args(*plan, d_keys, shift, d_table), kDigitShift, (hipStream_t)stream);
 }
 
 int rsort_pass_scan(const rsort_plan *plan, uint32_t *d_table, uint32_t *d_block_sums, void *stream) {
@@ -1081,7 +1070,7 @@ int rsort_pass_scan(const rsort_plan *plan, uint32_t *d_table, uint32_t *d_block
     if (st) return st;
     if (plan->n == 0) return RSORT_OK;
     if (!d_table || !d_block_sums) return RSORT_ERR_ARG;
-    return do_scan(*plan, d_table, d_block_sums, (hipStream_t)stream);
+    return run_scan(*plan, scan_args(*plan, d_table, d_block_sums), (hipStream_t)stream);
 }
 
 int rsort_pass_scatter(const rsort_plan *plan, const uint32_t *d_keys_in, const uint32_t *d_vals_in,
@@ -1093,8 +1082,8 @@ int rsort_pass_scatter(const rsort_plan *plan, const uint32_t *d_keys_in, const 
     if (plan->n == 0) return RSORT_OK;
     if (!d_keys_in || !d_keys_out || !d_table || (plan->pairs && (!d_vals_in || !d_vals_out)))
         return RSORT_ERR_ARG;
-    return do_scatter(*plan, d_keys_in, d_vals_in, d_keys_out, d_vals_out, shift, d_table, 0,
-                      kDigitShift, nullptr, 0, (hipStream_t)stream);
+    const PassIo io{d_keys_in, d_vals_in, d_keys_out, d_vals_out};
+    return run_scatter(*plan, scatter_args(*plan, io, shift, d_table), kDigitShift, (hipStream_t)stream);
 }
 
 int rsort_pass_local_sort(const rsort_plan *plan, const uint32_t *d_keys_in, const uint32_t *d_vals_in,
@@ -1107,9 +1096,9 @@ int rsort_pass_local_sort(const rsort_plan *plan, const uint32_t *d_keys_in, con
         return RSORT_ERR_ARG;
     if (d_keys_in == d_keys_out) return RSORT_ERR_ARG;
     // local-only mode never reads the offset table
-    const uint32_t *table = nullptr;
-    return do_scatter(*plan, d_keys_in, d_vals_in, d_keys_out, d_vals_out, shift, table, 1,
-                      kDigitShift, nullptr, 0, (hipStream_t)stream);
+    ScatterArgs a = scatter_args(*plan, PassIo{d_keys_in, d_vals_in, d_keys_out, d_vals_out}, shift, /*table=*/nullptr);
+    a.local_only = 1;
+    return run_scatter(*plan, a, kDigitShift, (hipStream_t)stream);
 }
 
 int rsort_set_rank_algo(int algo) {
@@ -1161,10 +1150,8 @@ int rsort_hybrid_report(const rsort_plan *plan, const void *d_workspace, int *re
     for (int i = 0; i < 4; ++i) report[i] = 0;
     if (plan->n == 0) return RSORT_OK;
     const Carve c = carve(*plan, const_cast<void *>(d_workspace));
-    hipStream_t s = (hipStream_t)stream;
     uint32_t h[4] = {0, 0, 0, 0};
-    if (hipMemcpyAsync(h, c.done + kHybMode, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess) return RSORT_ERR_HIP;
-    if (hipStreamSynchronize(s) != hipSuccess) return RSORT_ERR_HIP;
+    if ((st = read_words(h, c.done + kHybMode, 4, (hipStream_t)stream))) return st;
     report[0] = (int)h[kHybEligible - kHybMode];
     report[1] = (int)h[kHybGate - kHybMode];  // RSORT_GATE_*
     report[2] = (int)h[kHybMax - kHybMode];
@@ -1178,16 +1165,12 @@ int rsort_group_flags(const rsort_plan *plan, const void *d_workspace, int *flag
     if (st) return st;
     flags[0] = flags[1] = 0;
     if (!joint_plan(*plan) || plan->n == 0) return RSORT_OK;
-    const Carve c = carve(*plan, const_cast<void *>(d_workspace));
-    hipStream_t s = (hipStream_t)stream;
-    uint32_t h[2] = {0, 0};
-    for (int i = 0; i < 2; ++i)
-        if (2 * i + 1 < plan->passes &&
-            hipMemcpyAsync(&h[i], c.bounds + i * kBoundsWords, 4, hipMemcpyDeviceToHost, s) != hipSuccess)
-            return RSORT_ERR_HIP;
-    if (hipStreamSynchronize(s) != hipSuccess) return RSORT_ERR_HIP;
+    // (a digit-group plan has four passes: both odd passes' bounds exist)
+    uint32_t h[2 * kBoundsWords];
+    if ((st = read_words(h, carve(*plan, const_cast<void *>(d_workspace)).bounds, 2 * kBoundsWords, (hipStream_t)stream)))
+        return st;
     flags[0] = (int)h[0];  // kGroupsFixed / kGroupsWhole / kGroupsCut
-    flags[1] = (int)h[1];
+    flags[1] = (int)h[kBoundsWords];
     return RSORT_OK;
 }
 
@@ -1197,16 +1180,11 @@ int rsort_cut_plan_stats(const rsort_plan *plan, const void *d_workspace, int *s
     if (st) return st;
     for (int i = 0; i < 8; ++i) stats[i] = 0;
     if (!joint_plan(*plan) || plan->n == 0) return RSORT_OK;
-    const Carve c = carve(*plan, const_cast<void *>(d_workspace));
-    hipStream_t s = (hipStream_t)stream;
-    uint32_t h[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+    uint32_t h[2 * kBoundsWords];
+    if ((st = read_words(h, carve(*plan, const_cast<void *>(d_workspace)).bounds, 2 * kBoundsWords, (hipStream_t)stream)))
+        return st;
     for (int i = 0; i < 2; ++i)
-        if (2 * i + 1 < plan->passes &&
-            hipMemcpyAsync(h[i], c.bounds + i * kBoundsWords + kBoundsStat, 16, hipMemcpyDeviceToHost, s) != hipSuccess)
-            return RSORT_ERR_HIP;
-    if (hipStreamSynchronize(s) != hipSuccess) return RSORT_ERR_HIP;
-    for (int i = 0; i < 2; ++i)
-        for (int j = 0; j < 4; ++j) stats[4 * i + j] = (int)h[i][j];
+        for (int j = 0; j < 4; ++j) stats[4 * i + j] = (int)h[i * kBoundsWords + kBoundsStat + j];
     return RSORT_OK;
 }
 
@@ -1219,7 +1197,7 @@ int rsort_plan_features(const rsort_plan *plan) {
     if (joint_plan(p) && on) f |= RSORT_FEAT_GROUPS;
     if (next_plan(p) && on) {
         f |= RSORT_FEAT_NEXT_DIGIT;
-        f |= (!nx_tail() && p.num_chunks <= kRawTableMaxChunks) ? RSORT_FEAT_RAW_TABLES : RSORT_FEAT_TAIL_SCAN;
+        f |= (!lab().nx_tail && p.num_chunks <= kRawTableMaxChunks) ? RSORT_FEAT_RAW_TABLES : RSORT_FEAT_TAIL_SCAN;
     }
     return f;
 }
@@ -1234,11 +1212,9 @@ int rsort_plan_check(const rsort_plan *plan, const void *d_workspace, int *flags
     if (st) return st;
     *flags = 0;
     if (plan->n == 0) return RSORT_OK;
-    const Carve c = carve(*plan, const_cast<void *>(d_workspace));
-    hipStream_t s = (hipStream_t)stream;
     uint32_t h = 0;
-    if (hipMemcpyAsync(&h, c.done + kDoneErr, 4, hipMemcpyDeviceToHost, s) != hipSuccess) return RSORT_ERR_HIP;
-    if (hipStreamSynchronize(s) != hipSuccess) return RSORT_ERR_HIP;
+    if ((st = read_words(&h, carve(*plan, const_cast<void *>(d_workspace)).done + kDoneErr, 1, (hipStream_t)stream)))
+        return st;
     *flags = (int)(h & (kCheckTable | kCheckRankOrder));
     return RSORT_OK;
 }
@@ -1345,17 +1321,18 @@ int rsort_partition_device(const uint32_t *d_keys_in, const uint32_t *d_vals_in,
     if (!d_keys_in || !d_keys_out || !d_workspace || (pairs && !d_vals_out)) return RSORT_ERR_ARG;
     if (d_keys_in == d_keys_out) return RSORT_ERR_ARG;
     if (workspace_bytes < p.workspace_bytes) return RSORT_ERR_WORKSPACE;
-    const Carve c = carve(p, d_workspace);
+    const Carve c = carve(p, d_workspace, /*partition=*/true);
     const int ns = num_buckets - 1;
     // (the check words as a sort's: cleared by the histogram, the scatter's rank check recorded there)
-    if ((st = do_histogram(p, d_keys_in, 0, c.table, kDigitSplit, splitters, ns, s, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, c.done)))
-        return st;
-    if ((st = do_scan(p, c.table, c.bsums, s))) return st;
-    if ((st = do_scatter(p, d_keys_in, d_vals_in, d_keys_out, d_vals_out, 0, c.table, 0, kDigitSplit,
-                         splitters, ns, s, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr,
-                         c.done + kDoneErr)))
-        return st;
+    HistArgs h = hist_args(p, d_keys_in, 0, c.table);
+    ScatterArgs a = scatter_args(p, PassIo{d_keys_in, d_vals_in, d_keys_out, d_vals_out}, 0, c.table);
+    h.nsplit = a.nsplit = (uint32_t)ns;  // (the digit is a bucket: kDigitSplit)
+    for (int i = 0; i < ns; ++i) h.splitters[i] = a.splitters[i] = splitters[i];
+    h.done = c.done;
+    a.check = c.done + kDoneErr;
+    if ((st = run_histogram(p, h, kDigitSplit, s))) return st;
+    if ((st = run_scan(p, scan_args(p, c.table, c.bsums), s))) return st;
+    if ((st = run_scatter(p, a, kDigitSplit, s))) return st;
     return hip_status(launch_gather_starts(c.table, (uint32_t)p.num_chunks, (uint32_t)num_buckets,
                                            (uint64_t)n, d_bucket_starts, s));
 }
@@ -1368,11 +1345,9 @@ int rsort_partition_check(int64_t n, int num_buckets, int pairs, const void *d_w
                        /*partition=*/1);
     if (st) return st;
     if (n <= 0) return RSORT_OK;
-    const Carve c = carve(p, const_cast<void *>(d_workspace));
-    hipStream_t s = (hipStream_t)stream;
+    const Carve c = carve(p, const_cast<void *>(d_workspace), /*partition=*/true);
     uint32_t h = 0;
-    if (hipMemcpyAsync(&h, c.done + kDoneErr, 4, hipMemcpyDeviceToHost, s) != hipSuccess) return RSORT_ERR_HIP;
-    if (hipStreamSynchronize(s) != hipSuccess) return RSORT_ERR_HIP;
+    if ((st = read_words(&h, c.done + kDoneErr, 1, (hipStream_t)stream))) return st;
     *flags = (int)(h & (kCheckTable | kCheckRankOrder));
     return RSORT_OK;
 }
@@ -1388,8 +1363,8 @@ int rsort_top_histogram(const uint32_t *d_keys, int64_t n, int top_bits, uint32_
     if (!d_keys || !d_workspace) return RSORT_ERR_ARG;
     if (workspace_bytes < p.workspace_bytes) return RSORT_ERR_WORKSPACE;
     const Carve c = carve(p, d_workspace);
-    if ((st = do_histogram(p, d_keys, 32 - top_bits, c.table, kDigitShift, nullptr, 0, s))) return st;
-    if ((st = do_scan(p, c.table, c.bsums, s))) return st;
+    if ((st = run_histogram(p, hist_args(p, d_keys, 32 - top_bits, c.table), kDigitShift, s))) return st;
+    if ((st = run_scan(p, scan_args(p, c.table, c.bsums), s))) return st;
     hipError_t e = launch_gather_starts(c.table, (uint32_t)p.num_chunks, (uint32_t)p.bins,
                                         (uint64_t)n, c.starts, s);
     if (e != hipSuccess) return RSORT_ERR_HIP;

@@ -222,29 +222,42 @@ constexpr uint32_t kPieceNeg = 0x8000u;  // key range flag (slot word): counted 
 // 2^15 keys: chunk_keys / 2^15 <= 512 at n < 2^32)
 constexpr uint64_t kRowsWords = (uint64_t)kJointBins * kJointBins * kJointBins;
 constexpr uint32_t kMaxRowSpills = 512;
-// Upper bound of what a digit-group plan's workspace holds beyond any other plan's of the same n (the
-// joint counts, bounds, cut plan, piece counts and rows, each 256-B aligned): a caller that sizes a
-// workspace for one n and sorts a smaller one (the multi-GPU local sort) adds it.
-constexpr size_t kJointExtraBytes = ((size_t)kJointBins * kJointBins * 4 + 4 + 255) / 256 * 256 +
-                                    ((size_t)2 * kBoundsWords * 4 + 255) / 256 * 256 +
-                                    ((size_t)kPlanWords * 4 + 255) / 256 * 256 +
-                                    ((size_t)kPieceSlots * kJointBins * 4 + 255) / 256 * 256 +
-                                    ((size_t)kRowsWords + kJointBins * kJointBins) * 4;
+constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// What a digit-group plan's workspace holds beyond any other plan's of the same n, in layout order (the
+// workspace walk, carve in rsort_capi.cpp, takes each 256-B aligned).
+constexpr size_t kJointRegionBytes[] = {
+    (size_t)kJointBins * kJointBins * 4 + 4,                // joint counts [next digit][digit], rows counter
+    (size_t)2 * kBoundsWords * 4,                           // group bounds of passes 1 and 3
+    (size_t)kPlanWords * 4,                                 // cut plan
+    (size_t)kPieceSlots * kJointBins * 4,                   // its piece counts
+    ((size_t)kRowsWords + kJointBins * kJointBins) * 4};    // per-chunk joint-count rows (64 MiB), one-digit words
+constexpr size_t joint_extra_bytes() {
+    size_t b = 0;
+    for (size_t r : kJointRegionBytes) b += align256(r);
+    return b;
+}
+// Their sum: a caller that sizes a workspace for one n and sorts a smaller one (the multi-GPU local sort) adds it.
+constexpr size_t kJointExtraBytes = joint_extra_bytes();
 hipError_t launch_histogram_joint(const HistArgs &a, hipStream_t s);
 // From the joint counts [next digit][group]: the next pass's chunks into bounds[1..R+1] and its
 // mode into bounds[0] (above): kGroupsWhole when every group fits in max_keys keys, else the cut
 // plan (plan, pcounts rows zeroed); kGroupsFixed when the counts do not add up to n or enable
-// says the joint count was off (HistArgs::joint_enable). weighted != 0: a cut plan's chunks get
-// equal estimated cost instead of equal key counts (rs_joint_bounds).
-// ctab: the counting pass's scanned table; rows_cnt: HistArgs::rows_cnt (read and re-armed here);
-// rowone: the rows' one-digit words (HistArgs::rows + kRowsWords) -- all given and every chunk's rows
-// written: the cut plan's pieces are row tasks + their end keys (or direct adds).
-hipError_t launch_joint_bounds(const uint32_t *joint, const uint32_t *enable, uint32_t *bounds,
-                               uint32_t *plan, uint32_t *pcounts, uint64_t n, uint64_t max_keys,
-                               uint32_t snap, uint32_t weighted, hipStream_t s,
-                               const uint32_t *ctab = nullptr, uint32_t *rows_cnt = nullptr,
-                               const uint32_t *rowone = nullptr, const uint32_t *mode = nullptr,
-                               uint32_t mode_want = 0);
+// says the joint count was off (HistArgs::joint_enable).
+struct JointBoundsArgs {
+    const uint32_t *joint, *enable;
+    uint32_t *bounds, *plan, *pcounts;
+    uint64_t n, max_keys;
+    uint32_t snap;          // a cut-plan chunk boundary moves to a group boundary up to this many keys away
+    uint32_t weighted;      // != 0: a cut plan's chunks get equal estimated cost instead of equal key counts
+    // ctab: the counting pass's scanned table; rows_cnt: HistArgs::rows_cnt (read and re-armed here); rowone: the
+    // rows' one-digit words (HistArgs::rows + kRowsWords) -- all given and every chunk's rows written: the cut
+    // plan's pieces are row tasks + their end keys (or direct adds)
+    const uint32_t *ctab, *rowone;
+    uint32_t *rows_cnt;
+    const uint32_t *mode;   // hybrid-eligible sorts: as HistArgs::mode
+    uint32_t mode_want;
+};
+hipError_t launch_joint_bounds(const JointBoundsArgs &a, hipStream_t s);
 // rank_algo: internal RankAlgo. aligned16: the whole-line kernels may run -- keys-only: always
 // (any 4-B-aligned kout; launch_scatter shifts positions to kout's 128-B-aligned base); pairs: when
 // (vout - kout) % 16 == 0 (otherwise the same plan runs rs_scatter with the same tiles).
@@ -390,6 +403,17 @@ inline const char *lab_env(const char *name) {
     const char *lab = getenv("RSORT_LAB");
     if (lab == nullptr || lab[0] != '1') return nullptr;
     return getenv(name);
+}
+// A boolean lab switch: unset or empty -> def; "0..." -> off; anything else -> on.
+inline bool lab_flag(const char *name, bool def) {
+    const char *e = lab_env(name);
+    return (e == nullptr || e[0] == '\0') ? def : e[0] != '0';
+}
+// An integer lab switch: its value when inside [lo, hi], else def.
+inline long long lab_int(const char *name, long long lo, long long hi, long long def) {
+    const char *e = lab_env(name);
+    const long long x = e ? atoll(e) : lo - 1;
+    return (x >= lo && x <= hi) ? x : def;
 }
 
 }  // namespace rsort

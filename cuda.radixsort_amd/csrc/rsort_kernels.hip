@@ -2994,13 +2994,9 @@ hipError_t launch_histogram_joint(const HistArgs &a, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_joint_bounds(const uint32_t *joint, const uint32_t *enable, uint32_t *bounds,
-                               uint32_t *plan, uint32_t *pcounts, uint64_t n, uint64_t max_keys,
-                               uint32_t snap, uint32_t weighted, hipStream_t s, const uint32_t *ctab,
-                               uint32_t *rows_cnt, const uint32_t *rowone, const uint32_t *mode,
-                               uint32_t mode_want) {
-    rs_joint_bounds<<<1, 1024, 0, s>>>(joint, enable, bounds, plan, pcounts, n, max_keys, snap, weighted, ctab,
-                                       rows_cnt, rowone, mode, mode_want);
+hipError_t launch_joint_bounds(const JointBoundsArgs &a, hipStream_t s) {
+    rs_joint_bounds<<<1, 1024, 0, s>>>(a.joint, a.enable, a.bounds, a.plan, a.pcounts, a.n, a.max_keys, a.snap,
+                                       a.weighted, a.ctab, a.rows_cnt, a.rowone, a.mode, a.mode_want);
     return hipGetLastError();
 }
 
