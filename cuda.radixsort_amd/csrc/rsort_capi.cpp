@@ -32,6 +32,7 @@ std::atomic<int> g_group_chunks{1};
 std::atomic<int> g_table_fault{0};  // rsort_inject_table_fault (tests)
 std::atomic<int> g_rank_fault{0};   // rsort_inject_rank_fault (tests)
 std::atomic<int> g_hybrid{RSORT_HYBRID_AUTO};  // rsort_set_hybrid
+std::atomic<int> g_seg_grid_limit{0};  // rsort_set_segmented_grid_limit (tests); 0: no limit
 
 // Hybrid-eligible sorts enqueue both kernel sequences; every launch carries the device-side mode word and the
 // value it works under (HistArgs::mode). {nullptr, 0}: no test.
@@ -394,7 +395,10 @@ int check_plan(const rsort_plan *p) {
     if (!p) return RSORT_ERR_ARG;
     if (p->k_bits < kMinBits || p->k_bits > kMaxBits) return RSORT_ERR_BITS;
     if (p->n < 0 || p->n >= ((int64_t)1 << 32)) return RSORT_ERR_SIZE;
-    if (geom_from_shape(p->threads, p->tile_keys, p->pairs) < 0) return RSORT_ERR_ARG;
+    // the tile shape must be one a kernel of this digit width exists for (keys or pairs): a plan is the planner's,
+    // or a hand-made one that could be, never a shape that would only fail at its first launch
+    const int geom = geom_from_shape(p->threads, p->tile_keys, p->pairs);
+    if (geom < 0 || !scatter_shape_available(p->k_bits, p->pairs ? 1 : 0, geom)) return RSORT_ERR_ARG;
     if (p->tiles_per_chunk <= 0 || p->num_chunks <= 0 ||
         p->num_chunks * p->tiles_per_chunk * p->tile_keys < p->n ||
         p->chunk_keys != p->tiles_per_chunk * p->tile_keys || p->bins != (1 << p->k_bits) ||
@@ -819,6 +823,30 @@ bool seg_sizes_ok(int64_t n, int64_t nseg, int *st) {
     return *st == RSORT_OK;
 }
 
+int seg_rank() { return internal_rank(g_rank_algo.load()) == kRankAtomic ? kRankAtomic : kRankCount; }
+
+// The grid of every kind's kernel (seg_sort launches with it, rsort_segmented_grids reports it): the most
+// segments the kind can have, capped by four resident waves of workgroups -- the lists' lengths are only known on
+// the device, so the count comes from n and the segment count, and every workgroup strides over its list. The
+// test hook rsort_set_segmented_grid_limit caps every kind further.
+void seg_grids(int64_t n, int64_t nseg, int pairs, int rank, uint32_t grids[kSegKinds]) {
+    const int cus = std::max(1, device_cus());
+    const int limit = g_seg_grid_limit.load();
+    for (int kind = 0; kind < kSegKinds; ++kind) {
+        // each segment of a kind holds more keys than the kind below takes; a wave-kind workgroup sorts four
+        // segments at a time
+        const int below = kind == kSegSmall ? kSegWaveKeys : kind == kSegLds ? kSegSmallKeys : kind == kSegTiles ? kSegLdsKeys : 0;
+        int64_t most = below ? std::min<int64_t>(nseg, n / below) : nseg;
+        if (kind == kSegWave) most = (most + 3) / 4;
+        grids[kind] = 0;
+        if (most == 0) continue;
+        const int bpc = std::max(1, seg_blocks_per_cu(kind, pairs, rank));
+        int64_t grid = std::min<int64_t>(most, (int64_t)cus * bpc * 4);
+        if (limit > 0) grid = std::min<int64_t>(grid, limit);
+        grids[kind] = (uint32_t)grid;
+    }
+}
+
 int seg_sort(const uint32_t *kin, const uint32_t *vin, uint32_t *kout, uint32_t *vout, int64_t n,
              const uint32_t *off, int64_t nseg, void *ws, size_t ws_bytes, hipStream_t s) {
     int st;
@@ -832,7 +860,7 @@ int seg_sort(const uint32_t *kin, const uint32_t *vin, uint32_t *kout, uint32_t 
     const SegCarve c = seg_carve(n, nseg, pairs, ws);
     if (ws_bytes < c.bytes) return RSORT_ERR_WORKSPACE;
 
-    const int rank = internal_rank(g_rank_algo.load()) == kRankAtomic ? kRankAtomic : kRankCount;
+    const int rank = seg_rank();
     if (hipMemsetAsync(c.counters, 0, 256, s) != hipSuccess) return RSORT_ERR_HIP;
     {
         PhaseScope ps(RSORT_PHASE_HISTOGRAM, nseg, s);
@@ -844,18 +872,12 @@ int seg_sort(const uint32_t *kin, const uint32_t *vin, uint32_t *kout, uint32_t 
         a.num_segments = (uint32_t)nseg;
         if ((st = hip_status(launch_seg_classify(a, s)))) return st;
     }
-    // The lists' lengths are only known on the device: every kernel is launched with a grid from the segment
-    // count, the CU count and its occupancy, and one whose list is empty returns at once.
-    const int cus = std::max(1, device_cus());
+    // Every kernel is launched with seg_grids' grid; one whose list is empty returns at once.
+    uint32_t grids[kSegKinds];
+    seg_grids(n, nseg, pairs, rank, grids);
     for (int kind = 0; kind < kSegKinds; ++kind) {
-        // the most segments the kind can have: each holds more keys than the kind below takes; a wave-kind
-        // workgroup sorts four segments at a time
-        const int below = kind == kSegSmall ? kSegWaveKeys : kind == kSegLds ? kSegSmallKeys : kind == kSegTiles ? kSegLdsKeys : 0;
-        int64_t most = below ? std::min<int64_t>(nseg, n / below) : nseg;
-        if (kind == kSegWave) most = (most + 3) / 4;
-        if (most == 0) continue;
-        const int bpc = std::max(1, seg_blocks_per_cu(kind, pairs, rank));
-        const uint32_t grid = (uint32_t)std::min<int64_t>(most, (int64_t)cus * bpc * 4);
+        const uint32_t grid = grids[kind];
+        if (grid == 0) continue;
         PhaseScope ps(RSORT_PHASE_SCATTER, n, s);
         SegSortArgs a{};
         a.kin = kin;
@@ -1050,6 +1072,25 @@ int rsort_segmented_check(int64_t n, int64_t num_segments, int pairs, const void
     return RSORT_OK;
 }
 
+int rsort_segmented_grids(int64_t n, int64_t num_segments, int pairs, int *grids) {
+    int st;
+    if (!grids) return RSORT_ERR_ARG;
+    for (int i = 0; i < kSegKinds; ++i) grids[i] = 0;
+    if (!seg_sizes_ok(n, num_segments, &st)) return st;
+    if (n == 0 || num_segments == 0) return RSORT_OK;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return RSORT_ERR_NODEV;
+    uint32_t g[kSegKinds];
+    seg_grids(n, num_segments, pairs ? 1 : 0, seg_rank(), g);
+    for (int i = 0; i < kSegKinds; ++i) grids[i] = (int)g[i];
+    return RSORT_OK;
+}
+
+int rsort_set_segmented_grid_limit(int workgroups) {
+    if (workgroups < 0) return -RSORT_ERR_ARG;
+    return g_seg_grid_limit.exchange(workgroups);
+}
+
 int rsort_u32_segmented(const uint32_t *keys_in, const uint32_t *vals_in, uint32_t *keys_out, uint32_t *vals_out,
                         int64_t n, const uint32_t *offsets, int64_t num_segments) {
     return seg_host_sort(keys_in, vals_in, keys_out, vals_out, n, offsets, num_segments);
@@ -1222,6 +1263,8 @@ int rsort_plan_check(const rsort_plan *plan, const void *d_workspace, int *flags
 size_t rsort_scatter_kernels_used(char *buf, size_t len, int reset) {
     return scatter_kernels_used(buf, len, reset);
 }
+
+size_t rsort_scatter_kernels_known(char *buf, size_t len) { return scatter_kernels_known(buf, len); }
 
 int rsort_lane_order_probe(void) {
     int count = 0;

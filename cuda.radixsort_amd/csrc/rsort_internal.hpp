@@ -28,6 +28,8 @@ enum DigitMode : int { kDigitShift = 0, kDigitSplit = 1 };
 // through rs_scatter_pairs (128-B lines in both arrays), k = 5, 6 through rs_scatter_lines (64-B lines).
 // kGeomXL (k = 13): 4096-key tiles of 128 threads (2 waves), so the 2 x 8192 per-wave counters fit
 // in LDS beside the tile (112 KB keys-only).
+// kGeomLarge (512 x 32) holds an index but has no kernel: the planner never picks it, and check_plan refuses a plan
+// whose (k, pairs, shape) no kernel exists for.
 enum Geom : int { kGeomSmall = 0, kGeomLarge = 1, kGeomK4 = 2, kGeomLines = 3, kGeomLinesPairs = 4, kGeomXL = 5,
                   kGeomCount = 6 };
 struct GeomShape {
@@ -265,6 +267,9 @@ hipError_t launch_scatter(int bits, int pairs, int rank_algo, int dmode, int geo
                           const ScatterArgs &a, hipStream_t s);
 // Whether a (bits, pairs, rank_algo, dmode, geom) scatter kernel is compiled in.
 bool scatter_available(int bits, int pairs, int rank_algo, int dmode, int geom);
+// Whether any scatter kernel is compiled in for digits of `bits` bits on tiles of geometry `geom` (keys or pairs),
+// whatever the ranking and the digit mode: the shapes a plan may carry (check_plan).
+bool scatter_shape_available(int bits, int pairs, int geom);
 hipError_t launch_scan(const ScanArgs &a, hipStream_t s);
 hipError_t launch_gather_starts(const uint32_t *table, uint32_t num_chunks, uint32_t bins,
                                 uint64_t n, uint32_t *starts, hipStream_t s);
@@ -286,6 +291,9 @@ int scatter_blocks_per_cu(int bits, int pairs, int rank_algo, int geom, int dmod
 // Names of the scatter kernel instantiations launched since the last reset, ';'-joined into buf
 // (truncated to len - 1 characters); returns the full length. reset != 0 clears the record.
 size_t scatter_kernels_used(char *buf, size_t len, int reset);
+// Names of every scatter kernel instantiation the dispatch can hand out (its selection function over its whole
+// argument domain), ';'-joined like scatter_kernels_used. Host only: no device is needed.
+size_t scatter_kernels_known(char *buf, size_t len);
 // A kernel of another translation unit (the hybrid route's bucket kernel) for that record: registered by name
 // on first use and noted as launched.
 void note_kernel_used(const void *fn, const char *name);

@@ -2675,22 +2675,29 @@ template <int BITS, bool PAIRS>
 static void *scatter_pick2(int rank, int dmode, int geom, int aligned16) {
     if (rank != kRankSplit && rank != kRankAtomic && rank != kRankCount) return nullptr;
     if (dmode == kDigitSplit) {
-        if constexpr (BITS <= 5) {
-            if constexpr (BITS >= 2) {
-                // partition into 3..32 key ranges: whole lines from 4096-key tiles, like k = 3, 4
-                // (a digit's thread group must fit one wave: BITS >= 2)
-                constexpr int TH = kGeomShape[kGeomSmall].threads, KP = kGeomShape[kGeomSmall].kpt;
-                if (geom == kGeomSmall && rank == kRankAtomic && aligned16)
-                    return reg_lines<BITS, TH, KP, PAIRS ? kLineKeysPairs : kLineKeys,
-                                                                      PAIRS, kDigitSplit, PAIRS ? 2 : 3>();
-            }
+        // partitions into up to 32 key ranges. Their digit has 2..5 bits: a digit's thread group must fit one wave
+        // (partition_bits), so 4096-key tiles of 256 threads start at 2 bits, 8192-key tiles of 512 at 3.
+        if constexpr (BITS >= 2 && BITS <= 5) {
+            // whole lines from 4096-key tiles, like k = 3, 4. Two bits are at most four buckets: always the
+            // few-bucket ranking (CL = 2); three and more bits on these tiles are always more than four.
+            constexpr int TH = kGeomShape[kGeomSmall].threads, KP = kGeomShape[kGeomSmall].kpt;
+            if (geom == kGeomSmall && rank == kRankAtomic && aligned16)
+                return reg_lines<BITS, TH, KP, PAIRS ? kLineKeysPairs : kLineKeys, PAIRS, kDigitSplit, PAIRS ? 2 : 3,
+                                 BITS == 2 ? 2 : 0>();
             if constexpr (BITS >= 3 && !PAIRS) {
                 // keys-only partitions of large inputs: 8192-key tiles of 512 threads (kGeomK4's shape)
-                constexpr int TH = kGeomShape[kGeomK4].threads, KP = kGeomShape[kGeomK4].kpt;
+                constexpr int KT = kGeomShape[kGeomK4].threads, KK = kGeomShape[kGeomK4].kpt;
                 if (geom == kGeomK4 && rank == kRankAtomic && aligned16)
-                    return reg_lines<BITS, TH, KP, kLineKeys, false, kDigitSplit, 3>();
+                    return reg_lines<BITS, KT, KK, kLineKeys, false, kDigitSplit, 3>();
             }
-            if (geom == kGeomSmall && rank != kRankSplit) return scatter_cf<BITS, PAIRS, kDigitSplit, kGeomSmall>(rank);
+            if (geom == kGeomSmall && rank != kRankSplit) {
+                // a keys-only output on these tiles is always line-capable (n + 31 < 2^32: a partition that large
+                // takes kGeomK4): lane-ordered rs_scatter only serves pairs whose values lie no multiple of 16 B
+                // from the keys
+                if constexpr (PAIRS) return scatter_cf<BITS, true, kDigitSplit, kGeomSmall>(rank);
+                else if (rank == kRankCount) return scatter_fn<BITS, false, kRankCount, kDigitSplit, kGeomSmall>();
+                else return nullptr;
+            }
             if constexpr (BITS >= 3 && !PAIRS) {
                 if (geom == kGeomK4 && rank != kRankSplit) return scatter_cf<BITS, false, kDigitSplit, kGeomK4>(rank);
             }
@@ -2711,8 +2718,9 @@ static void *scatter_pick2(int rank, int dmode, int geom, int aligned16) {
         }
         return scatter_cf<BITS, PAIRS, kDigitShift, kGeomSmall>(rank);
     }
-    if constexpr (BITS >= 4 && BITS <= 8) {
-        if (geom == kGeomLarge) return scatter_cf<BITS, PAIRS, kDigitShift, kGeomLarge>(rank);
+    // (the planner hands out no kGeomLarge tiles, no line tiles for k = 4 pairs and kGeomK4's shape only to k <= 2
+    // sorts and to partitions: a shape it never picks has no kernel here, and check_plan refuses a plan carrying it)
+    if constexpr (BITS >= (PAIRS ? 5 : 4) && BITS <= 8) {
         // whole-line stores need lane-ordered atomics and 16-B aligned outputs; else the same
         // tiles through rs_scatter. Non-temporal (NT): keys-only loads and stores; pairs stores
         // only (dev/scatter_lab LAB_PAIRS, 2^30: 4.24 -> 3.96 ms; nt loads 4.66 ms)
@@ -2732,7 +2740,7 @@ static void *scatter_pick2(int rank, int dmode, int geom, int aligned16) {
             return scatter_cf<BITS, PAIRS, kDigitShift, GL>(rank);
         }
     }
-    if constexpr (BITS <= 4 && !PAIRS) {
+    if constexpr (BITS <= 2 && !PAIRS) {
         if (geom == kGeomK4) return scatter_cf<BITS, PAIRS, kDigitShift, kGeomK4>(rank);
     }
     return nullptr;
@@ -2754,7 +2762,7 @@ static void *scatter_pick(int pairs, int rank, int dmode, int geom, int aligned1
                  : scatter_pick2<BITS, false>(rank, dmode, geom, aligned16);
 }
 
-static void *scatter_kernel(int bits, int pairs, int rank, int dmode, int geom, int aligned16) {
+static void *scatter_base(int bits, int pairs, int rank, int dmode, int geom, int aligned16) {
     switch (bits) {
         case 1: return scatter_pick<1>(pairs, rank, dmode, geom, aligned16);
         case 2: return scatter_pick<2>(pairs, rank, dmode, geom, aligned16);
@@ -2771,6 +2779,91 @@ static void *scatter_kernel(int bits, int pairs, int rank, int dmode, int geom, 
         case 13: return scatter_pick<13>(pairs, rank, dmode, geom, aligned16);
         default: return nullptr;
     }
+}
+
+// THE selection: every scatter kernel a launch can run comes out of this function, and
+// scatter_kernels_known lists what it returns over its whole domain. Besides the plan's (bits, pairs, rank,
+// dmode, geom) and the outputs' line capability (aligned16) a launch depends on three more facts:
+//   upto26     n <= 2^26 keys
+//   few        a partition into fewer than four buckets (nsplit < 4)
+//   clustered  the launch carries a device-side cl_select flag (k = 8 digit-group passes)
+// fn == nullptr: no such kernel. twin != nullptr: the clustered-input variant launched behind fn (the flag
+// picks the one that works, the other leaves at once: ~3 us).
+struct ScatterPick {
+    void *fn, *twin;
+};
+
+static ScatterPick scatter_select(int bits, int pairs, int rank, int dmode, int geom, int aligned16,
+                                  bool upto26 = false, bool few = false, bool clustered = false) {
+    ScatterPick p{nullptr, nullptr};
+    if (geom < 0 || geom >= kGeomCount) return p;
+    void *fn = scatter_base(bits, pairs, rank, dmode, geom, aligned16);
+    if (!fn) return p;
+    // k = 3, 4 keys of up to 2^26 (the size measured): default-policy stores. A pass writes 256 MiB
+    // there, as much as the Infinity Cache holds (the two ping-pong buffers, 512 MiB, do NOT fit
+    // together), so part of what the next pass reads is still on die (dev/scatter_lab LAB_K4,
+    // 2^26 keys: 0.105 ms per pass against 0.113 with non-temporal stores; 2^30: 1.81 vs 1.75)
+    if (upto26 && !pairs && dmode == kDigitShift && geom == kGeomSmall && rank == kRankAtomic && aligned16 &&
+        (bits == 3 || bits == 4)) {
+        constexpr int TH = kGeomShape[kGeomSmall].threads, KP = kGeomShape[kGeomSmall].kpt;
+        fn = bits == 3 ? reg_lines<3, TH, KP, kLineKeys, false, kDigitShift, 1>()
+                       : reg_lines<4, TH, KP, kLineKeys, false, kDigitShift, 1>();
+    }
+    // keys-only partitions of large inputs into <= 4 buckets: the line kernel's few-bucket ranking instance (CL = 2;
+    // 4096-key tiles take it by their digit width alone, scatter_pick2)
+    if (dmode == kDigitSplit && few) {
+        constexpr int KT = kGeomShape[kGeomK4].threads, KK = kGeomShape[kGeomK4].kpt;
+        if (fn == reinterpret_cast<void *>(&rs_scatter_lines<3, KT, KK, kLineKeys, false, kDigitSplit, 3>))
+            fn = reg_lines<3, KT, KK, kLineKeys, false, kDigitSplit, 3, 2>();
+    }
+    p.fn = fn;
+    // clustered-input variants of the k = 8 line kernels (rank_add_hot)
+    if (clustered) {
+        constexpr int PT = kGeomShape[kGeomLinesPairs].threads, PK = kGeomShape[kGeomLinesPairs].kpt;
+        if (fn == reinterpret_cast<void *>(&rs_scatter_lines<8, 1024, 16, kLineKeys, false, kDigitShift, 3>))
+            p.twin = reg_lines<8, 1024, 16, kLineKeys, false, kDigitShift, 3, 1>();
+        else if (fn == reinterpret_cast<void *>(&rs_scatter_lines<8, PT, PK, kLineKeysPairs, true, kDigitShift, 2>))
+            p.twin = reg_lines<8, PT, PK, kLineKeysPairs, true, kDigitShift, 2, 1>();
+    }
+    return p;
+}
+
+// The kernel a plan's launches run when none of the three facts holds (occupancy, availability).
+static void *scatter_kernel(int bits, int pairs, int rank, int dmode, int geom, int aligned16) {
+    return scatter_select(bits, pairs, rank, dmode, geom, aligned16).fn;
+}
+
+size_t scatter_kernels_known(char *buf, size_t len) {
+    std::vector<const void *> seen;
+    auto add = [&seen](const void *fn) {
+        if (fn != nullptr && std::find(seen.begin(), seen.end(), fn) == seen.end()) seen.push_back(fn);
+    };
+    for (int bits = kMinBits; bits <= kMaxBits; ++bits)
+        for (int pairs = 0; pairs < 2; ++pairs)
+            for (int rank : {(int)kRankSplit, (int)kRankCount, (int)kRankAtomic})
+                for (int dmode : {(int)kDigitShift, (int)kDigitSplit})
+                    for (int geom = 0; geom < kGeomCount; ++geom)
+                        for (int facts = 0; facts < 16; ++facts) {
+                            const ScatterPick p = scatter_select(bits, pairs, rank, dmode, geom, facts & 1,
+                                                                 (facts & 2) != 0, (facts & 4) != 0, (facts & 8) != 0);
+                            add(p.fn);
+                            add(p.twin);
+                        }
+    std::lock_guard<std::mutex> g(g_kn_mu);
+    std::string out;
+    for (const void *fn : seen)
+        for (auto &kv : g_kn_names)
+            if (kv.first == fn) {
+                if (!out.empty()) out += ";";
+                out += kv.second;
+                break;
+            }
+    if (buf && len > 0) {
+        const size_t m = std::min(len - 1, out.size());
+        memcpy(buf, out.data(), m);
+        buf[m] = '\0';
+    }
+    return out.size();
 }
 
 
@@ -2910,47 +3003,21 @@ bool scatter_available(int bits, int pairs, int rank_algo, int dmode, int geom) 
     return scatter_kernel(bits, pairs, rank_algo, dmode, geom, 1) != nullptr;
 }
 
+bool scatter_shape_available(int bits, int pairs, int geom) {
+    for (int rank : {(int)kRankSplit, (int)kRankCount, (int)kRankAtomic})
+        for (int dmode : {(int)kDigitShift, (int)kDigitSplit})
+            for (int aligned16 = 0; aligned16 < 2; ++aligned16)
+                if (scatter_select(bits, pairs, rank, dmode, geom, aligned16).fn != nullptr) return true;
+    return false;
+}
+
 hipError_t launch_scatter(int bits, int pairs, int rank_algo, int dmode, int geom, int aligned16,
                           const ScatterArgs &a, hipStream_t s) {
     if (geom < 0 || geom >= kGeomCount) return hipErrorInvalidValue;
-    void *fn = scatter_kernel(bits, pairs, rank_algo, dmode, geom, aligned16);
+    const ScatterPick pick = scatter_select(bits, pairs, rank_algo, dmode, geom, aligned16, a.n <= ((uint64_t)1 << 26),
+                                            a.nsplit < 4u, a.cl_select != nullptr);
+    void *fn = pick.fn, *cl = pick.twin;
     if (!fn) return hipErrorInvalidValue;
-    // k = 3, 4 keys of up to 2^26 (the size measured): default-policy stores. A pass writes 256 MiB
-    // there, as much as the Infinity Cache holds (the two ping-pong buffers, 512 MiB, do NOT fit
-    // together), so part of what the next pass reads is still on die (dev/scatter_lab LAB_K4,
-    // 2^26 keys: 0.105 ms per pass against 0.113 with non-temporal stores; 2^30: 1.81 vs 1.75)
-    if (a.n <= ((uint64_t)1 << 26) && !pairs && dmode == kDigitShift && geom == kGeomSmall &&
-        rank_algo == kRankAtomic && aligned16 && (bits == 3 || bits == 4)) {
-        constexpr int TH = kGeomShape[kGeomSmall].threads, KP = kGeomShape[kGeomSmall].kpt;
-        fn = bits == 3 ? reg_lines<3, TH, KP, kLineKeys, false, kDigitShift, 1>()
-                       : reg_lines<4, TH, KP, kLineKeys, false, kDigitShift, 1>();
-    }
-    // partitions into <= 4 buckets: the line kernel's few-bucket ranking instance (CL = 2)
-    if (dmode == kDigitSplit && a.nsplit < 4u) {
-        constexpr int ST = kGeomShape[kGeomSmall].threads, SK = kGeomShape[kGeomSmall].kpt;
-        constexpr int KT = kGeomShape[kGeomK4].threads, KK = kGeomShape[kGeomK4].kpt;
-        if (fn == reinterpret_cast<void *>(&rs_scatter_lines<2, ST, SK, kLineKeys, false, kDigitSplit, 3>))
-            fn = reg_lines<2, ST, SK, kLineKeys, false, kDigitSplit, 3, 2>();
-        else if (fn == reinterpret_cast<void *>(&rs_scatter_lines<3, ST, SK, kLineKeys, false, kDigitSplit, 3>))
-            fn = reg_lines<3, ST, SK, kLineKeys, false, kDigitSplit, 3, 2>();
-        else if (fn == reinterpret_cast<void *>(&rs_scatter_lines<2, ST, SK, kLineKeysPairs, true, kDigitSplit, 2>))
-            fn = reg_lines<2, ST, SK, kLineKeysPairs, true, kDigitSplit, 2, 2>();
-        else if (fn == reinterpret_cast<void *>(&rs_scatter_lines<3, ST, SK, kLineKeysPairs, true, kDigitSplit, 2>))
-            fn = reg_lines<3, ST, SK, kLineKeysPairs, true, kDigitSplit, 2, 2>();
-        else if (fn == reinterpret_cast<void *>(&rs_scatter_lines<3, KT, KK, kLineKeys, false, kDigitSplit, 3>))
-            fn = reg_lines<3, KT, KK, kLineKeys, false, kDigitSplit, 3, 2>();
-    }
-    // clustered-input variants of the k = 8 line kernels (rank_add_hot): both kernels are launched,
-    // the device-side flag *cl_select picks the one that works (the other leaves at once: ~3 us)
-    void *cl = nullptr;
-    if (a.cl_select != nullptr) {
-        constexpr int PT = kGeomShape[kGeomLinesPairs].threads, PK = kGeomShape[kGeomLinesPairs].kpt;
-        if (fn == reinterpret_cast<void *>(&rs_scatter_lines<8, 1024, 16, kLineKeys, false, kDigitShift, 3>))
-            cl = reg_lines<8, 1024, 16, kLineKeys, false, kDigitShift, 3, 1>();
-        else if (fn == reinterpret_cast<void *>(&rs_scatter_lines<8, PT, PK, kLineKeysPairs, true, kDigitShift, 2>))
-            cl = reg_lines<8, PT, PK, kLineKeysPairs, true, kDigitShift, 2, 1>();
-
-    }
     // digit-group chunks, next-digit counts and raw tables exist only in the whole-line kernels: any
     // other kernel would read the unscanned counts (or the group bounds) as offsets -- refuse, never
     // sort wrongly

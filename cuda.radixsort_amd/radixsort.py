@@ -194,6 +194,7 @@ SIGNATURES = {
     "rsort_inject_table_fault": ([_int], _int),
     "rsort_inject_rank_fault": ([_int], _int),
     "rsort_scatter_kernels_used": ([ctypes.c_char_p, _sz, _int], _sz),
+    "rsort_scatter_kernels_known": ([ctypes.c_char_p, _sz], _sz),
     "rsort_profile_begin": ([], _int),
     "rsort_profile_end": ([ctypes.POINTER(PhaseTimes)], _int),
     "rsort_partition_workspace_size": ([_i64, _int, _int], _sz),
@@ -237,6 +238,8 @@ SIGNATURES = {
     "rsort_u32_segmented_device": ([_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _sz, _vp], _int),
     "rsort_segmented_check": ([_i64, _i64, _int, _vp, ctypes.POINTER(_int), ctypes.POINTER(_i64), _vp], _int),
     "rsort_u32_segmented": ([_vp, _vp, _vp, _vp, _i64, _vp, _i64], _int),
+    "rsort_segmented_grids": ([_i64, _i64, _int, ctypes.POINTER(_int)], _int),
+    "rsort_set_segmented_grid_limit": ([_int], _int),
     "rsort_vendor_segmented_workspace_size": ([_i64, _i64], _sz),
     "rsort_u32_vendor_segmented_device": ([_vp, _vp, _i64, _vp, _i64, _vp, _sz, _vp], _int),
     "rsort_fingerprint_device": ([_vp, _vp, _i64, _vp, _vp], _int),
@@ -530,6 +533,16 @@ def scatter_kernels_used(reset: bool = False) -> list[str]:
     n = int(_lib().rsort_scatter_kernels_used(None, 0, 0))
     buf = ctypes.create_string_buffer(n + 1)
     _lib().rsort_scatter_kernels_used(buf, n + 1, 1 if reset else 0)
+    s = buf.value.decode()
+    return s.split(";") if s else []
+
+
+def scatter_kernels_known() -> list[str]:
+    """Every scatter kernel instantiation the dispatch can launch (rsort_scatter_kernels_known): its selection
+    function over its whole domain. Host only."""
+    n = int(_lib().rsort_scatter_kernels_known(None, 0))
+    buf = ctypes.create_string_buffer(n + 1)
+    _lib().rsort_scatter_kernels_known(buf, n + 1)
     s = buf.value.decode()
     return s.split(";") if s else []
 
@@ -991,6 +1004,30 @@ def segmented_check(n: int, num_segments: int, pairs: bool, ws, stream=None) -> 
     _check(_lib().rsort_segmented_check(int(n), int(num_segments), 1 if pairs else 0, _ptr(ws), ctypes.byref(f), cc,
                                         _stream(stream)), "rsort_segmented_check")
     return int(f.value), {k: int(cc[i]) for i, k in enumerate(SEG_CLASSES)}
+
+
+SEG_KERNELS = ("wave", "small", "lds", "tiles")
+
+
+def segmented_grids(n: int, num_segments: int, pairs: bool = False) -> dict:
+    """rsort_segmented_grids: the workgroups each of the four kernels of a segmented sort with these arguments is
+    launched with now ({"wave", "small", "lds", "tiles"}; a wave-kind workgroup sorts four segments at a time)."""
+    g = (ctypes.c_int * 4)()
+    _check(_lib().rsort_segmented_grids(int(n), int(num_segments), 1 if pairs else 0, g), "rsort_segmented_grids")
+    return {k: int(g[i]) for i, k in enumerate(SEG_KERNELS)}
+
+
+@contextmanager
+def segmented_grid_limit(workgroups: int):
+    """TEST HOOK (rsort_set_segmented_grid_limit): every segmented-sort kernel runs with at most `workgroups`
+    workgroups, so each strides over its list; the previous setting comes back on exit."""
+    old = int(_lib().rsort_set_segmented_grid_limit(int(workgroups)))
+    if old < 0:
+        raise RSortError(-old, "rsort_set_segmented_grid_limit")
+    try:
+        yield
+    finally:
+        _lib().rsort_set_segmented_grid_limit(old)
 
 
 def sortSegmentsByDevice(keys, offsets, out, vals=None, vals_out=None):

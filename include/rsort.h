@@ -139,7 +139,9 @@ RSORT_API int rsort_u32_pairs_device(const uint32_t *d_keys_in, const uint32_t *
                                      uint32_t *d_keys_out, uint32_t *d_vals_out, int64_t n,
                                      int k_bits, void *d_workspace, size_t workspace_bytes,
                                      void *stream);
-/* Same, with an explicit plan (from rsort_plan_make) -- lets tests pin the geometry. */
+/* Same, with an explicit plan (from rsort_plan_make) -- lets tests pin the geometry. Every entry point that
+ * takes a plan checks it first: RSORT_ERR_ARG for inconsistent fields and for a (k_bits, pairs, threads x tile_keys)
+ * no scatter kernel exists for -- a plan is the planner's, or one the planner could have made. */
 /* rsort_sort_planned with flags: RSORT_SORT_NO_HYBRID keeps this sort off the hybrid route (rsort_set_hybrid)
  * whatever the process-wide setting says. */
 #define RSORT_SORT_NO_HYBRID 1
@@ -379,12 +381,30 @@ RSORT_API int rsort_inject_table_fault(int enable);
  * of order), and the check catches it: rsort_plan_check reports bit 1 (RSORT_CHECK_RANK_ORDER), the host
  * entries return RSORT_ERR_CHECK. Process-wide; returns the previous setting. */
 RSORT_API int rsort_inject_rank_fault(int enable);
+/* The workgroups rsort_u32_segmented_device launches each of its four kernels with, for a call with these
+ * arguments on the current device under the current process settings (rsort_set_rank_algo, the limit below):
+ * grids[0..3] = the one-wave kernel (four segments per workgroup), the small workgroup shape, the large one, the
+ * multi-tile kernel; 0 where the arguments allow no segment of the kind. Each is min(the most segments of the
+ * kind that n keys in num_segments segments can hold, CUs x resident workgroups per CU x 4): a list longer than
+ * its grid is strided over. The sort and this report share one computation. RSORT_ERR_NODEV without a device
+ * (the occupancy is the device's). */
+RSORT_API int rsort_segmented_grids(int64_t n, int64_t num_segments, int pairs, int *grids);
+/* TEST HOOK (never set in production): workgroups > 0 caps the grid of every segmented-sort kernel, so small
+ * inputs make each workgroup (or wave) sort several segments in turn; 0 (the default) is no limit. Process-wide;
+ * returns the previous setting, or -RSORT_ERR_ARG for a negative value (nothing changes). */
+RSORT_API int rsort_set_segmented_grid_limit(int workgroups);
 /* The scatter kernel instantiations this library has launched since the last reset, ';'-joined
  * into buf (at most len - 1 characters and a NUL); returns the full length. reset != 0 clears the
  * record. A k = 8 digit-group sort launches a plain and a clustered-input kernel for each pass
  * after the first (the device picks one, the other leaves at once): both are listed. A hybrid-eligible sort
  * (rsort_set_hybrid) lists the bucket kernel rs_bucket_sort16 too; rsort_hybrid_report says whether it worked. */
 RSORT_API size_t rsort_scatter_kernels_used(char *buf, size_t len, int reset);
+/* The names of every scatter kernel instantiation the library's dispatch can launch: what its one selection
+ * function returns over its whole argument domain (digit bits, keys / pairs, ranking, digit mode, tile shape,
+ * line-capable outputs, n <= 2^26, fewer than four partition buckets, a clustered-input twin), ';'-joined as
+ * above; returns the full length. Runs on the host alone: no device is needed. Every name
+ * rsort_scatter_kernels_used reports is one of these, rs_bucket_sort16 (the hybrid route's own kernel) apart. */
+RSORT_API size_t rsort_scatter_kernels_known(char *buf, size_t len);
 /* 1 if the current device's LDS returns same-address atomic adds in lane order (the default
  * ranking relies on it and falls back to ballots otherwise), 0 if not, < 0 on error. The
  * probe runs once per device (a few microseconds) and is cached. It allocates and synchronises: before a

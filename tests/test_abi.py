@@ -76,6 +76,63 @@ def test_plan_rejects(n, k, status):
     assert e.value.status == status
 
 
+def _shaped(n, k, pairs, threads, tile_keys):
+    """The planner's plan for (n, k, pairs) moved to another tile shape, every derived field kept consistent."""
+    p = rs.plan(n, k, pairs)
+    p.threads, p.tile_keys = threads, tile_keys
+    tiles = max(1, -(-n // tile_keys))
+    p.tiles_per_chunk = max(1, -(-tiles // 512))
+    p.chunk_keys = p.tiles_per_chunk * tile_keys
+    p.num_chunks = -(-tiles // p.tiles_per_chunk)
+    p.table_entries = p.bins * p.num_chunks
+    return p
+
+
+def test_plan_shape_without_a_kernel_is_rejected():
+    """check_plan (every entry point that takes a plan) answers RSORT_ERR_ARG for a (k, pairs, tile shape) no
+    scatter kernel exists for -- the shapes the planner never picks -- instead of failing at the first launch."""
+    n = 1 << 24
+    feat = lambda p: rs._lib().rsort_plan_features(ctypes.byref(p))  # noqa: E731
+    # (an n = 0 plan: rsort_pass_scan returns right after the plan check, RSORT_OK for a valid one)
+    scan = lambda k, pairs, th, tile: rs._lib().rsort_pass_scan(  # noqa: E731
+        ctypes.byref(_shaped(0, k, pairs, th, tile)), None, None, None)
+    no_kernel = [(k, pairs, 512, 16384) for k in (4, 5, 6, 7, 8) for pairs in (False, True)]  # 512 x 32: no kernel at all
+    no_kernel += [(6, False, 512, 8192), (1, True, 512, 8192)]   # 512 x 16: keys only, k <= 5
+    no_kernel += [(4, True, 1024, 8192)]                         # pair line tiles: k = 5..8
+    no_kernel += [(13, False, 256, 4096), (8, False, 128, 4096), (9, False, 1024, 16384), (3, True, 1024, 8192)]
+    for k, pairs, th, tile in no_kernel:
+        p = _shaped(n, k, pairs, th, tile)
+        assert feat(p) == -1, (k, pairs, th, tile)
+        assert scan(k, pairs, th, tile) == 1, (k, pairs, th, tile)
+    with pytest.raises(rs.RSortError) as e:
+        rs.plan_features(_shaped(n, 6, False, 512, 16384))
+    assert e.value.status == 1
+    # the same moves onto shapes that do have a kernel stay valid plans
+    have = [(1, False, 512, 8192), (2, False, 512, 8192), (4, False, 1024, 16384), (8, False, 1024, 16384),
+            (5, True, 1024, 8192), (8, True, 1024, 8192), (12, True, 256, 4096), (13, True, 128, 4096),
+            (3, False, 512, 8192), (5, False, 512, 8192)]  # (the last two: keys-only partitions' shape and bits)
+    for k, pairs, th, tile in have:
+        p = _shaped(n, k, pairs, th, tile)
+        assert feat(p) >= 0, (k, pairs, th, tile)
+        assert scan(k, pairs, th, tile) == 0, (k, pairs, th, tile)
+    # every plan the planner makes passes
+    for k in range(1, 14):
+        for pairs in (False, True):
+            for nn in (1, 70001, 1 << 24, 1 << 28, (1 << 32) - 1):
+                assert feat(rs.plan(nn, k, pairs)) >= 0, (k, pairs, nn)
+
+
+def test_scatter_kernels_known_is_host_only_and_closed():
+    known = rs.scatter_kernels_known()
+    assert len(known) == len(set(known)) and len(known) > 100
+    assert all(re.fullmatch(r"rs_scatter(_lines|_pairs)?<[\w, ]+>", k) for k in known), known
+    assert not any(k.startswith("rs_scatter<") and ", 512, 32," in k for k in known)  # no 512 x 32 tiles
+    lib = rs._lib()
+    n = int(lib.rsort_scatter_kernels_known(None, 0))
+    buf = ctypes.create_string_buffer(8)
+    assert int(lib.rsort_scatter_kernels_known(buf, 8)) == n and buf.value == ";".join(known).encode()[:7]
+
+
 def test_device_entry_validates_before_touching_the_gpu():
     lib = rs._lib()
     # bad k, bad n: rejected before any HIP call

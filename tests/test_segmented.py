@@ -140,6 +140,36 @@ def test_capacities():
     assert rs._lib().rsort_segmented_capacity(0, None, None) == 1
 
 
+def test_grid_entries_validate():
+    lib = rs._lib()
+    g = (ctypes.c_int * 4)(7, 7, 7, 7)
+    assert lib.rsort_segmented_grids(10, 2, 0, None) == 1
+    assert lib.rsort_segmented_grids(-1, 2, 0, g) == 3 and list(g) == [0, 0, 0, 0]
+    assert lib.rsort_segmented_grids(1 << 32, 2, 0, g) == 3
+    assert lib.rsort_segmented_grids(10, -1, 0, g) == 1
+    assert lib.rsort_segmented_grids(10, 1 << 31, 1, g) == 1
+    # nothing to sort: no kernel is launched, and no device is needed to say so
+    for n, s in ((0, 5), (10, 0)):
+        g[:] = [7, 7, 7, 7]
+        assert lib.rsort_segmented_grids(n, s, 0, g) == 0 and list(g) == [0, 0, 0, 0]
+    if not gpu_available():
+        assert lib.rsort_segmented_grids(1000, 3, 0, g) == 8  # the occupancy is a device's
+    # the limit: 0 by default, the previous value comes back, a negative one is refused and changes nothing
+    assert lib.rsort_set_segmented_grid_limit(-1) == -1
+    assert lib.rsort_set_segmented_grid_limit(3) == 0
+    assert lib.rsort_set_segmented_grid_limit(-5) == -1
+    assert lib.rsort_set_segmented_grid_limit(0) == 3
+    with rs.segmented_grid_limit(2):
+        with rs.segmented_grid_limit(1):
+            assert lib.rsort_set_segmented_grid_limit(1) == 1
+        assert lib.rsort_set_segmented_grid_limit(2) == 2
+    assert lib.rsort_set_segmented_grid_limit(0) == 0
+    with pytest.raises(rs.RSortError):
+        with rs.segmented_grid_limit(-2):
+            pass
+    assert lib.rsort_set_segmented_grid_limit(0) == 0
+
+
 def test_python_constants():
     assert rs.CHECK_OFFSETS == 4 and rs.CHECK_RANK_ORDER == 2
     assert rs.SEG_CLASSES == ("small", "lds", "tiles", "rejected")
