@@ -205,6 +205,22 @@ __device__ __forceinline__ void peer_mask(uint32_t d, uint32_t &mlo, uint32_t &m
     }
 }
 
+// Ranking of one whole-wave slot: adds its 64 BITS-bit digits to the wave's counter row and returns each lane's
+// stable rank among the row's keys of its digit so far: rank_add, or (kRankCount) the ballot peer match.
+template <int BITS, int RANK>
+__device__ __forceinline__ uint32_t slot_rank(uint32_t *row, uint32_t d) {
+    if constexpr (RANK == kRankAtomic) {
+        return rank_add(row, d);
+    } else {
+        uint32_t mlo, mhi;
+        peer_mask<BITS>(d, mlo, mhi);
+        const uint32_t pre = __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, 0u));
+        const uint32_t old = row[d];
+        if (pre == 0) row[d] = old + (uint32_t)(__builtin_popcount(mlo) + __builtin_popcount(mhi));
+        return old + pre;
+    }
+}
+
 // Per-tile check of the kRankAtomic premise (the reference checks every sort,
 // Parallel7.cu:679-687). The line and pairs kernels and rs_scatter run it on the first slot of a full tile
 // (every kRankCheckEvery-th tile of a chunk): each lane's rank r from the lane-ordered returning adds must

@@ -36,6 +36,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1400,13 +1401,10 @@ __global__ __launch_bounds__(THREADS, MINW > 0 ? MINW : 1) void rs_scatter(Scatt
                     if constexpr (PAIRS) s_vals[p] = val[j];
                     continue;
                 }
-                uint32_t mlo, mhi;
-                peer_mask<BITS>(d, mlo, mhi);
-                const uint32_t pre = __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, 0u));
-                const uint32_t old = s_cnt[w * R + d];
-                if (pre == 0) s_cnt[w * R + d] = old + (uint32_t)(__builtin_popcount(mlo) + __builtin_popcount(mhi));
-                s_keys[old + pre] = key[j];
-                if constexpr (PAIRS) s_vals[old + pre] = val[j];
+                // (kRankAtomic above calls rank_add itself: through slot_rank its schedule changes, dev/LOG.md)
+                const uint32_t p = slot_rank<BITS, kRankCount>(&s_cnt[w * R], d);
+                s_keys[p] = key[j];
+                if constexpr (PAIRS) s_vals[p] = val[j];
             }
             __syncthreads();
             if (nb < cend) load_tile(nb, key, val);
@@ -1585,8 +1583,81 @@ __device__ bool raw_offsets(const uint32_t *table, uint32_t C, uint32_t c, uint6
     return tot == n;
 }
 
-// ------------------------------------------------------------------------------ small kernels
-// starts[d] = scanned table[d][0] (global start of digit d), starts[bins] = n.
+// ------------------------------------------------------------------------------ tile phases
+// What rs_scatter_lines and rs_scatter_pairs do in the same way, written once: per-tile header, rank packing,
+// tile loader, chunk window. Step 1, step 2's gather and the output quad stay in each kernel: as functions they
+// cost registers in some instances or missed the timing gate (DESIGN.md §3 "Shared tile phases").
+// Per-tile header. check_tile: the rank check runs on every kRankCheckEvery-th tile of a chunk, its first included
+// (workgroup-uniform). full: every slot of every lane holds a key of this chunk (no per-slot predicates).
+struct TileMask {
+    bool check_tile, full, h0;
+    uint32_t plim;  // opaque lane-relative limit
+    // slot j holds a real key: j * 64 < plim and, in slot 0, the lane's tile position is not before the chunk (head)
+    __device__ __forceinline__ bool real(int j) const { return (uint32_t)(j * kWave) < plim && (j != 0 || h0); }
+};
+// The header of the tno-th tile of a chunk, at tb; `head`: the chunk's for its first tile, 0 after it.
+template <uint32_t T>
+__device__ __forceinline__ TileMask tile_mask(uint64_t tb, uint64_t tno, uint64_t cend, uint32_t base, uint32_t head) {
+    TileMask m;
+    m.check_tile = (tno & (kRankCheckEvery - 1)) == 0;
+    const uint32_t valid = (uint32_t)min<uint64_t>((uint64_t)T, cend - tb);
+    m.full = valid == T && head == 0;
+    m.plim = valid > base ? valid - base : 0u;
+    asm volatile("" : "+v"(m.plim));  // opaque: not rebuilt from `valid` at every use
+    m.h0 = base >= head;
+    return m;
+}
+
+// Two ranks (< 2^16) per register `pair`: slot j's in half j % 2 of rk[j / 2] (the even slot is written first).
+__device__ __forceinline__ void pack_rank(uint32_t &pair, int j, uint32_t r) { pair = (j & 1) ? (pair | (r << 16)) : r; }
+
+// Tile loader (wave-striped: slot j of the lane at tile position `base` holds position base + 64 j). The lane
+// offset is made opaque: one lane offset + immediate slot offsets, nothing hoisted out of the tile loop. Positions
+// at or past cend read as 0 (masked by TileMask::real). NTL: non-temporal loads (dev/scatter_lab experiment).
+template <int THREADS, int KPT, bool PAIRS, bool NTL>
+__device__ __forceinline__ void load_line_tile(const ScatterArgs &a, uint64_t tb, const uint64_t &cend,
+                                               const uint32_t &base, uint32_t (&k)[KPT], uint32_t (&v)[PAIRS ? KPT : 1]) {
+    constexpr uint32_t T = THREADS * KPT;
+    const uint32_t valid = (uint32_t)min<uint64_t>((uint64_t)T, cend - tb);
+    uint32_t lb = base;
+    asm volatile("" : "+v"(lb));
+    const uint32_t *__restrict__ tk = a.kin + tb + lb;
+    const uint32_t *__restrict__ tv = PAIRS ? a.vin + tb + lb : nullptr;
+    if (valid == T) {
+#pragma unroll
+        for (int j = 0; j < KPT; ++j) {
+            k[j] = NTL ? __builtin_nontemporal_load(tk + j * kWave) : tk[j * kWave];
+            if constexpr (PAIRS) v[j] = NTL ? __builtin_nontemporal_load(tv + j * kWave) : tv[j * kWave];
+        }
+    } else {
+        const uint32_t lim = valid > lb ? valid - lb : 0u;
+#pragma unroll
+        for (int j = 0; j < KPT; ++j) {
+            const bool in = (uint32_t)(j * kWave) < lim;
+            k[j] = in ? tk[j * kWave] : 0u;
+            if constexpr (PAIRS) v[j] = in ? tv[j * kWave] : 0u;
+        }
+    }
+}
+
+// The keys [cbeg, cend) of workgroup c: chunk c of chunk_keys keys, or a digit-group chunk (rs_histogram_joint)
+// [b, cend) from a.bounds with any start b: its tiles start at the 256-B boundary below b (wave loads stay whole
+// 128-B lines), the first skips its `head` keys (the previous chunk's), and it may end in a partial tile.
+struct ChunkWindow { uint64_t cbeg, cend; uint32_t head; };
+__device__ __forceinline__ ChunkWindow chunk_window(const ScatterArgs &a, uint32_t c) {
+    ChunkWindow cw;
+    cw.cbeg = (uint64_t)c * a.chunk_keys;
+    cw.cend = min(cw.cbeg + a.chunk_keys, a.n);
+    cw.head = 0;
+    if (a.bounds != nullptr && a.bounds[0] != 0u) {
+        const uint64_t b = a.bounds[1 + c];
+        cw.cend = a.bounds[2 + c];
+        cw.cbeg = b < cw.cend ? (b & ~(uint64_t)(kWave - 1)) : cw.cend;
+        cw.head = (uint32_t)(b < cw.cend ? b - cw.cbeg : 0);
+    }
+    return cw;
+}
+
 // ------------------------------------------------------------------------------ scatter (line-combining)
 // rs_scatter_lines: the same pass as rs_scatter (Parallel7.cu:193-316 fused), built so that every
 // global store is a whole, aligned G-key line written by 16-B-per-lane store instructions.
@@ -1609,7 +1680,7 @@ __device__ bool raw_offsets(const uint32_t *table, uint32_t C, uint32_t c, uint6
 // chunk's output, so that line is written with a lane mask; after the chunk's last tile the
 // remaining carries are flushed with masked dword stores (both lines are shared with the
 // neighbouring chunks' output). Only the grid's very last tile is partial (chunks are whole
-// tiles), so the full-tile paths carry no per-slot predicates.
+// tiles), so the full-tile paths carry no per-slot predicates. (Shared with rs_scatter_pairs: the tile phases above.)
 template <int BITS, int THREADS, int KPT, int G, bool PAIRS, int DMODE, int NT = 0, int CL = 0>
 __global__ __launch_bounds__(THREADS, THREADS == 256 ? hooks::kLinesMinWavesSmall : 1) void rs_scatter_lines(ScatterArgs a) {
     constexpr uint32_t R = 1u << BITS;
@@ -1618,7 +1689,6 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? hooks::kLinesMinWavesSmal
     constexpr uint32_t T = THREADS * KPT;
     constexpr uint32_t TPD = THREADS / R;            // threads per digit
     constexpr uint32_t CAP = T + (G - 1) * R;        // staged keys incl. carries, worst case
-    constexpr uint32_t NL = CAP / G;
     constexpr uint32_t QPL = G / 4;                  // 16-B quads per line
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     static_assert(R <= THREADS && TPD <= kWave && (G == 16 || G == 32),
@@ -1665,57 +1735,24 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? hooks::kLinesMinWavesSmal
     constexpr bool STAB = DMODE == kDigitSplit && BITS > 3;
     __shared__ uint32_t s_stab[STAB ? kSplitTabWords : 1];
     const Digit<BITS, DMODE> dig{a.shift, a.nsplit, a.splitters, STAB ? s_stab : nullptr};
-    uint64_t cbeg = (uint64_t)c * a.chunk_keys;
-    uint64_t cend = min(cbeg + a.chunk_keys, a.n);
-    uint32_t head = 0;  // leading keys of the first tile that belong to the previous chunk
     // clustered-pass selection (ScatterArgs::cl_select): the plain and the clustered kernel are both
     // launched, and the one not selected by the device-side flag leaves at once
     if (a.cl_select != nullptr && ((*a.cl_select != kGroupsWhole) != (CL != 0))) return;
     if (a.mode != nullptr && *a.mode != a.mode_want) return;  // hybrid-eligible sorts: the other route runs
     RS_WG_T0
-    if (a.bounds != nullptr && a.bounds[0] != 0u) {
-        // digit-group chunk (rs_histogram_joint): any start, so the tiles start at the 256-B
-        // boundary below it (every wave load stays two whole 128-B lines), the first tile skips
-        // its `head` keys, and every chunk may end in a partial tile
-        const uint64_t b = a.bounds[1 + c];
-        cend = a.bounds[2 + c];
-        cbeg = b < cend ? (b & ~(uint64_t)(kWave - 1)) : cend;
-        head = (uint32_t)(b < cend ? b - cbeg : 0);
-    }
+    const ChunkWindow cw = chunk_window(a, c);
+    const uint64_t cbeg = cw.cbeg, cend = cw.cend;
+    uint32_t head = cw.head;  // leading keys of the first tile that belong to the previous chunk
 
     // digit group of this thread: digit d = t / TPD; the leader (sub == 0) keeps the state
     const uint32_t d_own = t / TPD;
     const uint32_t sub = t % TPD;
     const bool leader = sub == 0;
-    const uint32_t glead = lane & ~(TPD - 1u);
     uint32_t g_run = 0, carry = 0, inv = 0, nb_own = 0;  // (nb_own: the leader's s_nb entry)
     const uint32_t base = w * SEG + lane;
-    auto load_tile = [&](uint64_t tb, uint32_t (&k)[KPT], uint32_t (&v)[PAIRS ? KPT : 1]) {
-        const uint32_t valid = (uint32_t)min<uint64_t>((uint64_t)T, cend - tb);
-        uint32_t lb = base;  // opaque: one lane offset + immediate slot offsets, nothing hoisted
-        asm volatile("" : "+v"(lb));
-        const uint32_t *__restrict__ tk = a.kin + tb + lb;
-        const uint32_t *__restrict__ tv = PAIRS ? a.vin + tb + lb : nullptr;
-        if (valid == T) {
-#pragma unroll
-            for (int j = 0; j < KPT; ++j) {
-                // NT & 1: non-temporal key/value loads (dev/scatter_lab experiment)
-                k[j] = (NT & 1) ? __builtin_nontemporal_load(tk + j * kWave) : tk[j * kWave];
-                if constexpr (PAIRS) v[j] = (NT & 1) ? __builtin_nontemporal_load(tv + j * kWave) : tv[j * kWave];
-            }
-        } else {
-            const uint32_t lim = valid > lb ? valid - lb : 0u;
-#pragma unroll
-            for (int j = 0; j < KPT; ++j) {
-                const bool in = (uint32_t)(j * kWave) < lim;
-                k[j] = in ? tk[j * kWave] : 0u;
-                if constexpr (PAIRS) v[j] = in ? tv[j * kWave] : 0u;
-            }
-        }
-    };
     uint32_t key[KPT];
     uint32_t val[PAIRS ? KPT : 1];
-    if (cbeg < cend) load_tile(cbeg, key, val);
+    if (cbeg < cend) load_line_tile<THREADS, KPT, PAIRS, (NT & 1) != 0>(a, cbeg, cend, base, key, val);
     if constexpr (STAB) {
         dig.fill_table(t, THREADS);  // (while the first tile's loads are in flight)
         __syncthreads();
@@ -1838,21 +1875,14 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? hooks::kLinesMinWavesSmal
     uint32_t order_bad = 0;       // the per-tile rank check (rank_check) failed in this thread
 
     for (uint64_t tb = cbeg, tno = 0; tb < cend; tb += T, ++tno) {
-        // the rank check on every kRankCheckEvery-th tile of a chunk, its first included (workgroup-uniform)
-        const bool check_tile = (tno & (kRankCheckEvery - 1)) == 0;
-        const uint32_t valid = (uint32_t)min<uint64_t>((uint64_t)T, cend - tb);
-        const bool full = valid == T && head == 0;
-        const uint64_t nb = tb + T;
-        uint32_t plim = valid > base ? valid - base : 0u;  // slot j is real iff j * 64 < plim
-        asm volatile("" : "+v"(plim));
-        // ... and, in slot 0, iff this lane's tile position is not before the chunk (head)
-        const bool h0 = base >= head;
+        const TileMask tm = tile_mask<T>(tb, tno, cend, base, head);
         head = 0;
+        const uint64_t nb = tb + T;
         // ---- 1. per-wave digit histogram (each wave clears its own counters first)
 #pragma unroll
         for (uint32_t i = lane; i < R; i += kWave) s_cnt[w * RS + i] = 0;
         // rank first: the returning add IS the key's rank among its wave's keys of that digit
-        // (lane order, kRankAtomic); two ranks (< 2^16) per register
+        // (lane order, kRankAtomic); two ranks per register (pack_rank)
         uint32_t rk[(KPT + 1) / 2];
         // split digits (a compare per splitter) are kept from step 1, 4 bits each, for step 3
         constexpr bool PD = DMODE == kDigitSplit && BITS <= 4;
@@ -1862,7 +1892,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? hooks::kLinesMinWavesSmal
         uint32_t nkey[KPT];
         uint32_t nval[PAIRS ? KPT : 1];
         constexpr int DB = CL ? hooks::kDeferKeysCl : hooks::kDeferKeysPlain;
-        if (full && DB > 0 && !PD) {
+        if (tm.full && DB > 0 && !PD) {
             // deferred ranking: batches of DB slots issue their adds, then turn the returns into ranks
             static_assert(DB == 0 || KPT % (DB > 0 ? DB : 1) == 0, "whole batches");
 #pragma unroll
@@ -1876,11 +1906,11 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? hooks::kLinesMinWavesSmal
                 for (int u = 0; u < DB; ++u) {
                     const int j = j0 + u;
                     uint32_t r = hot_rank(o[u], dig(key[j]), cc[u], mm[u]);
-                    if (j == 0 && check_tile) order_bad |= rank_check<BITS>(dig(key[j]), r, a.rank_fault);
-                    rk[j / 2] = (j & 1) ? (rk[j / 2] | (r << 16)) : r;
+                    if (j == 0 && tm.check_tile) order_bad |= rank_check<BITS>(dig(key[j]), r, a.rank_fault);
+                    pack_rank(rk[j / 2], j, r);
                 }
             }
-        } else if (full && FEW) {
+        } else if (tm.full && FEW) {
             // partitions into <= 4 buckets (CL = 2, launch_scatter): 16-32 lanes of a slot share each digit,
             // and lane-ordered adds serialised them on one LDS counter (2^30 keys into 2 buckets: 2.8 ms
             // against 1.8 for 8). Here the wave's running count of each digit is a wave-uniform register:
@@ -1899,11 +1929,11 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? hooks::kLinesMinWavesSmal
                         r = c4[v] + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
                     c4[v] += wave_count(m);
                 }
-                if (j == 0 && check_tile) order_bad |= rank_check<BITS>(dj, r, a.rank_fault);
-                rk[j / 2] = (j & 1) ? (rk[j / 2] | (r << 16)) : r;
+                if (j == 0 && tm.check_tile) order_bad |= rank_check<BITS>(dj, r, a.rank_fault);
+                pack_rank(rk[j / 2], j, r);
             }
             if (lane < 4u) s_cnt[w * RS + lane] = lane == 0u ? c4[0] : lane == 1u ? c4[1] : lane == 2u ? c4[2] : c4[3];
-        } else if (full) {
+        } else if (tm.full) {
 #pragma unroll
             for (int j = 0; j < KPT; ++j) {
                 // (measured: rank_add's aggregation is ~2% faster than plain lane-ordered adds even
@@ -1911,8 +1941,8 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? hooks::kLinesMinWavesSmal
                 const uint32_t dj = dig(key[j]);
                 if constexpr (PD) dpk[j / 8] |= dj << (4 * (j % 8));
                 uint32_t r = CL ? rank_add_hot(&s_cnt[w * RS], dj, hotd) : rank_add(&s_cnt[w * RS], dj);
-                if (j == 0 && check_tile) order_bad |= rank_check<BITS>(dj, r, a.rank_fault);
-                rk[j / 2] = (j & 1) ? (rk[j / 2] | (r << 16)) : r;
+                if (j == 0 && tm.check_tile) order_bad |= rank_check<BITS>(dj, r, a.rank_fault);
+                pack_rank(rk[j / 2], j, r);
             }
         } else {
 #pragma unroll
@@ -1920,19 +1950,20 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? hooks::kLinesMinWavesSmal
                 const uint32_t d = dig(key[j]);
                 if constexpr (PD) dpk[j / 8] |= d << (4 * (j % 8));
                 uint32_t r = 0;
-                if ((uint32_t)(j * kWave) < plim && (j != 0 || h0)) r = atomicAdd(&s_cnt[w * RS + d], 1u);
-                rk[j / 2] = (j & 1) ? (rk[j / 2] | (r << 16)) : r;
+                if (tm.real(j)) r = atomicAdd(&s_cnt[w * RS + d], 1u);
+                pack_rank(rk[j / 2], j, r);
             }
         }
         // next tile's keys: in flight through the scan, staging and output phases
-        if (nb < cend) load_tile(nb, nkey, nval);
+        if (nb < cend) load_line_tile<THREADS, KPT, PAIRS, (NT & 1) != 0>(a, nb, cend, base, nkey, nval);
         __syncthreads();
 
         // ---- 2. segments, line records, carry copy, counter bases
         // the group's TPD threads split the W per-wave counters of digit d; the leader combines
         constexpr uint32_t WPT = (W >= (int)TPD) ? W / TPD : 1;   // waves per group thread
-        uint32_t part = 0;
         uint32_t wx[WPT];
+        uint32_t gpre, cnt;
+        uint32_t part = 0;
         if (sub < (uint32_t)W) {
 #pragma unroll
             for (uint32_t i = 0; i < WPT; ++i) {
@@ -1941,9 +1972,6 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? hooks::kLinesMinWavesSmal
                 part += wx[i];
             }
         }
-        // exclusive prefix of the parts inside the group and the digit's tile count (the group is
-        // TPD consecutive lanes of one wave)
-        uint32_t gpre, cnt;
         group_scan<TPD>(part, sub, gpre, cnt);
         uint32_t wcnt = 0, A = 0, e = 0;
         if (leader) {
@@ -2054,7 +2082,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? hooks::kLinesMinWavesSmal
             for (int u = 0; u < SB; ++u) {
                 const int j = j0 + u;
                 uint32_t idx = pp[u] < ll[u] ? pp[u] : CAP + dd[u] * G + (pp[u] - ll[u]);
-                if (!(full || ((uint32_t)(j * kWave) < plim && (j != 0 || h0)))) idx = CAP + R * G;  // scratch slot
+                if (!(tm.full || tm.real(j))) idx = CAP + R * G;  // scratch slot
                 s_stage[idx] = key[j];
                 if constexpr (PAIRS) s_vstage[idx] = val[j];
             }
@@ -2135,7 +2163,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? hooks::kLinesMinWavesSmal
 //   4. whole lines out (8 lanes x 16 B per array per line), the tails read back into registers
 // A chunk starts with `inv` invalid leading slots per digit (its first line begins before the
 // chunk's output) and ends with masked dword stores of the carries (both lines are shared with the
-// neighbouring chunks). Digit-group chunks (a.bounds) and the clustered-input ranking (CL) as in
+// neighbouring chunks). Digit-group chunks (a.bounds; tile_mask) and the clustered-input ranking (CL) as in
 // rs_scatter_lines. (The measured variants of this kernel -- two tiles of loads in flight, interleaved or
 // sequential staging, deferred output, other load points -- are dev/pairs_variants.hpp.)
 template <int BITS, int THREADS, int KPT, int CL = 0>
@@ -2171,16 +2199,10 @@ __global__ __launch_bounds__(THREADS, 1) void rs_scatter_pairs(ScatterArgs a) {
     const uint32_t lane = lane_id();
     const uint32_t c = blockIdx.x;
     const Digit<BITS, kDigitShift> dig{a.shift, 0, nullptr};
-    uint64_t cbeg = (uint64_t)c * a.chunk_keys;
-    uint64_t cend = min(cbeg + a.chunk_keys, a.n);
-    uint32_t head = 0;
-    if (a.cl_select != nullptr && ((*a.cl_select != kGroupsWhole) != (CL != 0))) return;
-    if (a.bounds != nullptr && a.bounds[0] != 0u) {
-        const uint64_t b = a.bounds[1 + c];
-        cend = a.bounds[2 + c];
-        cbeg = b < cend ? (b & ~(uint64_t)(kWave - 1)) : cend;
-        head = (uint32_t)(b < cend ? b - cbeg : 0);
-    }
+    if (a.cl_select != nullptr && ((*a.cl_select != kGroupsWhole) != (CL != 0))) return;  // (as rs_scatter_lines)
+    const ChunkWindow cw = chunk_window(a, c);
+    const uint64_t cbeg = cw.cbeg, cend = cw.cend;
+    uint32_t head = cw.head;
 
     const uint32_t d_own = t / TPD;
     const uint32_t sub = t % TPD;
@@ -2199,28 +2221,6 @@ __global__ __launch_bounds__(THREADS, 1) void rs_scatter_pairs(ScatterArgs a) {
     for (uint32_t i = 0; i < CPT; ++i) ck[i] = cv[i] = 0u;
 
     const uint32_t base = w * SEG + lane;
-    auto load_tile = [&](uint64_t tb, uint32_t (&k)[KPT], uint32_t (&v)[KPT]) {
-        const uint32_t valid = (uint32_t)min<uint64_t>((uint64_t)T, cend - tb);
-        uint32_t lb = base;
-        asm volatile("" : "+v"(lb));
-        const uint32_t *__restrict__ tk = a.kin + tb + lb;
-        const uint32_t *__restrict__ tv = a.vin + tb + lb;
-        if (valid == T) {
-#pragma unroll
-            for (int j = 0; j < KPT; ++j) {
-                k[j] = tk[j * kWave];
-                v[j] = tv[j * kWave];
-            }
-        } else {
-            const uint32_t lim = valid > lb ? valid - lb : 0u;
-#pragma unroll
-            for (int j = 0; j < KPT; ++j) {
-                const bool in = (uint32_t)(j * kWave) < lim;
-                k[j] = in ? tk[j * kWave] : 0u;
-                v[j] = in ? tv[j * kWave] : 0u;
-            }
-        }
-    };
 
     // the digit of whole line V: the last marked line start at or before V
     auto line_digit = [&](uint32_t V) {
@@ -2281,25 +2281,19 @@ __global__ __launch_bounds__(THREADS, 1) void rs_scatter_pairs(ScatterArgs a) {
     uint32_t hotd = 0xFFFFFFFFu;
     uint32_t order_bad = 0;  // the per-tile rank check (rank_check) failed in this thread
     uint32_t key[KPT], val[KPT];
-    if (cbeg < cend) load_tile(cbeg, key, val);
+    if (cbeg < cend) load_line_tile<THREADS, KPT, true, false>(a, cbeg, cend, base, key, val);
     for (uint64_t tb = cbeg, tno = 0; tb < cend; tb += T, ++tno) {
-        // the rank check on every kRankCheckEvery-th tile of a chunk, its first included (workgroup-uniform)
-        const bool check_tile = (tno & (kRankCheckEvery - 1)) == 0;
-        const uint32_t valid = (uint32_t)min<uint64_t>((uint64_t)T, cend - tb);
-        const bool full = valid == T && head == 0;
-        const uint64_t nb = tb + T;
-        uint32_t plim = valid > base ? valid - base : 0u;
-        asm volatile("" : "+v"(plim));
-        const bool h0 = base >= head;
+        const TileMask tm = tile_mask<T>(tb, tno, cend, base, head);
         head = 0;
+        const uint64_t nb = tb + T;
         // ---- 1. per-wave digit histogram; the returning add is the key's rank among its wave's
-        //      keys of that digit (lane order, kRankAtomic); two ranks per register
+        //      keys of that digit (lane order, kRankAtomic); two ranks per register (pack_rank)
 #pragma unroll
         for (uint32_t i = lane; i < R; i += kWave) s_cnt[w * RS + i] = 0;
         uint32_t rk[(KPT + 1) / 2];
         uint32_t nkey[KPT], nval[KPT];
         constexpr int DB = hooks::kDeferPairs;
-        if (full && DB > 0) {
+        if (tm.full && DB > 0) {
             // deferred ranking (hot_issue / hot_rank): the slots' adds back to back, one LDS wait
             // per batch of DB slots (C4: 3.45 vs 3.48 ms per pass, dev/lab.sh ab)
             static_assert(DB == 0 || KPT % (DB > 0 ? DB : 1) == 0, "whole batches");
@@ -2314,31 +2308,31 @@ __global__ __launch_bounds__(THREADS, 1) void rs_scatter_pairs(ScatterArgs a) {
                 for (int u = 0; u < DB; ++u) {
                     const int j = j0 + u;
                     uint32_t r = hot_rank(o[u], dig(key[j]), cc[u], mm[u]);
-                    if (j == 0 && check_tile) order_bad |= rank_check<BITS>(dig(key[j]), r, a.rank_fault);
-                    rk[j / 2] = (j & 1) ? (rk[j / 2] | (r << 16)) : r;
+                    if (j == 0 && tm.check_tile) order_bad |= rank_check<BITS>(dig(key[j]), r, a.rank_fault);
+                    pack_rank(rk[j / 2], j, r);
                 }
             }
-        } else if (full) {
+        } else if (tm.full) {
 #pragma unroll
             for (int j = 0; j < KPT; ++j) {
                 const uint32_t dj = dig(key[j]);
                 uint32_t r = CL ? rank_add_hot(&s_cnt[w * RS], dj, hotd) : rank_add(&s_cnt[w * RS], dj);
-                if (j == 0 && check_tile) order_bad |= rank_check<BITS>(dj, r, a.rank_fault);
-                rk[j / 2] = (j & 1) ? (rk[j / 2] | (r << 16)) : r;
+                if (j == 0 && tm.check_tile) order_bad |= rank_check<BITS>(dj, r, a.rank_fault);
+                pack_rank(rk[j / 2], j, r);
             }
         } else {
 #pragma unroll
             for (int j = 0; j < KPT; ++j) {
                 const uint32_t d = dig(key[j]);
                 uint32_t r = 0;
-                if ((uint32_t)(j * kWave) < plim && (j != 0 || h0)) r = atomicAdd(&s_cnt[w * RS + d], 1u);
-                rk[j / 2] = (j & 1) ? (rk[j / 2] | (r << 16)) : r;
+                if (tm.real(j)) r = atomicAdd(&s_cnt[w * RS + d], 1u);
+                pack_rank(rk[j / 2], j, r);
             }
         }
         RS_STAMP(5);
         // the next tile's loads: in flight through steps 2-4 (issued earlier or later measured slower,
         // dev/pairs_variants.hpp)
-        if (nb < cend) load_tile(nb, nkey, nval);
+        if (nb < cend) load_line_tile<THREADS, KPT, true, false>(a, nb, cend, base, nkey, nval);
         // (the previous tile's step 4 has read the bitmap, records and staging area: behind the
         // barrier below)
         __syncthreads();
@@ -2346,8 +2340,9 @@ __global__ __launch_bounds__(THREADS, 1) void rs_scatter_pairs(ScatterArgs a) {
 
         // ---- 2. segments, bases, carry in, line marks
         constexpr uint32_t WPT = (W >= (int)TPD) ? W / TPD : 1;
-        uint32_t part = 0;
         uint32_t wx[WPT];
+        uint32_t gpre, cnt;
+        uint32_t part = 0;
         if (sub < (uint32_t)W) {
 #pragma unroll
             for (uint32_t i = 0; i < WPT; ++i) {
@@ -2356,7 +2351,6 @@ __global__ __launch_bounds__(THREADS, 1) void rs_scatter_pairs(ScatterArgs a) {
                 part += wx[i];
             }
         }
-        uint32_t gpre, cnt;
         group_scan<TPD>(part, sub, gpre, cnt);
         // (carry, g_run, inv are the same in every thread of the group)
         const uint32_t A = g_run - carry;          // line-aligned
@@ -2423,7 +2417,7 @@ __global__ __launch_bounds__(THREADS, 1) void rs_scatter_pairs(ScatterArgs a) {
             for (int u = 0; u < SB; ++u) {
                 const int j = j0 + u;
                 uint32_t idx = pp[u];
-                if (!(full || ((uint32_t)(j * kWave) < plim && (j != 0 || h0)))) idx = CAP + 32;  // sink
+                if (!(tm.full || tm.real(j))) idx = CAP + 32;  // sink
                 s_k[idx] = key[j];
                 s_v[idx] = val[j];
             }
@@ -2579,31 +2573,37 @@ __global__ void rs_gen_iota(uint32_t *out, uint64_t n, uint32_t base) {
 }
 
 // ------------------------------------------------------------------------------ dispatch
-// Kernel pointers with their names recorded (rsort_scatter_kernels_used).
+// Kernel pointers with their names recorded (rsort_scatter_kernels_used), once per instance; lines: is_line_kernel.
+__attribute__((format(printf, 3, 4))) static void *name_kernel(void *fn, bool lines, const char *fmt, ...) {
+    char nm[96];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(nm, sizeof nm, fmt, ap);
+    va_end(ap);
+    register_kernel(fn, nm, lines);
+    return fn;
+}
+
 template <int BITS, int THREADS, int KPT, int G, bool PAIRS, int DMODE, int NT = 0, int CL = 0>
 static void *reg_lines() {
-    void *fn = reinterpret_cast<void *>(&rs_scatter_lines<BITS, THREADS, KPT, G, PAIRS, DMODE, NT, CL>);
-    static const bool once = [fn] {
-        char nm[96];
-        snprintf(nm, sizeof nm, "rs_scatter_lines<%d, %d, %d, %d, %s, %d, %d, %d>", BITS, THREADS, KPT, G,
-                 PAIRS ? "true" : "false", DMODE, NT, CL);
-        register_kernel(fn, nm, true);
-        return true;
-    }();
-    (void)once;
+    static void *const fn = name_kernel(reinterpret_cast<void *>(&rs_scatter_lines<BITS, THREADS, KPT, G, PAIRS, DMODE, NT, CL>),
+                                        true, "rs_scatter_lines<%d, %d, %d, %d, %s, %d, %d, %d>", BITS, THREADS, KPT, G,
+                                        PAIRS ? "true" : "false", DMODE, NT, CL);
     return fn;
 }
 
 template <int BITS, int THREADS, int KPT, int CL = 0>
 static void *reg_pairs() {
-    void *fn = reinterpret_cast<void *>(&rs_scatter_pairs<BITS, THREADS, KPT, CL>);
-    static const bool once = [fn] {
-        char nm[96];
-        snprintf(nm, sizeof nm, "rs_scatter_pairs<%d, %d, %d, %d>", BITS, THREADS, KPT, CL);
-        register_kernel(fn, nm, true);
-        return true;
-    }();
-    (void)once;
+    static void *const fn = name_kernel(reinterpret_cast<void *>(&rs_scatter_pairs<BITS, THREADS, KPT, CL>), true,
+                                        "rs_scatter_pairs<%d, %d, %d, %d>", BITS, THREADS, KPT, CL);
+    return fn;
+}
+
+template <int BITS, int THREADS, int KPT, bool PAIRS, int RANK, int DMODE, int MINW>
+static void *reg_scatter() {
+    static void *const fn = name_kernel(reinterpret_cast<void *>(&rs_scatter<BITS, THREADS, KPT, PAIRS, RANK, DMODE, MINW>),
+                                        false, "rs_scatter<%d, %d, %d, %s, %d, %d, %d>", BITS, THREADS, KPT,
+                                        PAIRS ? "true" : "false", RANK, DMODE, MINW);
     return fn;
 }
 
@@ -2615,20 +2615,6 @@ static bool pairs_lines64() {
         return e != nullptr && e[0] != '\0' && e[0] != '0';
     }();
     return v;
-}
-
-template <int BITS, int THREADS, int KPT, bool PAIRS, int RANK, int DMODE, int MINW>
-static void *reg_scatter() {
-    void *fn = reinterpret_cast<void *>(&rs_scatter<BITS, THREADS, KPT, PAIRS, RANK, DMODE, MINW>);
-    static const bool once = [fn] {
-        char nm[96];
-        snprintf(nm, sizeof nm, "rs_scatter<%d, %d, %d, %s, %d, %d, %d>", BITS, THREADS, KPT, PAIRS ? "true" : "false",
-                 RANK, DMODE, MINW);
-        register_kernel(fn, nm);
-        return true;
-    }();
-    (void)once;
-    return fn;
 }
 
 template <int BITS>

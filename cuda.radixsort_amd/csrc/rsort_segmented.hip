@@ -67,24 +67,6 @@ __global__ __launch_bounds__(256) void rs_seg_classify(SegClassifyArgs a) {
     }
 }
 
-// ------------------------------------------------------------------------------ ranking of one whole-wave slot
-// Adds the slot's 64 digits to the wave's counter row and returns each lane's stable rank among the row's keys
-// of its digit so far. kRankAtomic: one lane-ordered returning LDS add (rank_add); kRankCount: the ballot peer
-// match -- the digit's first lane bumps the counter for all its peers.
-template <int RANK>
-__device__ __forceinline__ uint32_t slot_rank(uint32_t *row, uint32_t d) {
-    if constexpr (RANK == kRankAtomic) {
-        return rank_add(row, d);
-    } else {
-        uint32_t mlo, mhi;
-        peer_mask<8>(d, mlo, mhi);
-        const uint32_t pre = __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, 0u));
-        const uint32_t old = row[d];
-        if (pre == 0) row[d] = old + (uint32_t)(__builtin_popcount(mlo) + __builtin_popcount(mhi));
-        return old + pre;
-    }
-}
-
 // ------------------------------------------------------------------------------ the store of a sorted segment
 // o[4q .. 4q + 3] = x[4q .. 4q + 3] for the quads covering x[a, a + n): o is the segment's output moved down by
 // a < 4 words to a 16-B boundary, so whole quads inside the segment go out as 16-B stores and the words at its
@@ -141,7 +123,7 @@ __global__ __launch_bounds__(256) void rs_seg_wave(SegSortArgs a) {
                 rk[j] = 0;
                 if ((uint32_t)(j * kWave) < n) {  // (wave-uniform: the slot holds a key; lanes past n hold pads)
                     const uint32_t d = (key[j] >> sh) & 255u;
-                    rk[j] = slot_rank<RANK>(row, d);
+                    rk[j] = slot_rank<8, RANK>(row, d);
                     if constexpr (RANK == kRankAtomic) {
                         if (j == 0 && (uint32_t)kWave <= n) order_bad |= rank_check<8>(d, rk[j], a.rank_fault);
                     }
@@ -226,7 +208,7 @@ __global__ __launch_bounds__(THREADS) void rs_seg_lds(SegSortArgs a) {
                 // (wave-uniform: the slot holds a key; its lanes past n hold pads)
                 if ((uint32_t)(j * kWave) < span && w * span + j * kWave < n) {
                     const uint32_t d = (key[j] >> sh) & 255u;
-                    rk[j] = slot_rank<RANK>(row, d);
+                    rk[j] = slot_rank<8, RANK>(row, d);
                     if constexpr (RANK == kRankAtomic) {
                         if (j == 0 && w * span + kWave <= n) order_bad |= rank_check<8>(d, rk[j], a.rank_fault);
                     }
@@ -335,7 +317,7 @@ __global__ __launch_bounds__(1024) void rs_seg_tiles(SegSortArgs a) {
                     rk[j] = 0;
                     if (w * SPAN + j * kWave < nt) {  // (wave-uniform; pads only in the segment's last slot)
                         const uint32_t d = (key[j] >> sh) & 255u;
-                        rk[j] = slot_rank<RANK>(row, d);
+                        rk[j] = slot_rank<8, RANK>(row, d);
                         if constexpr (RANK == kRankAtomic) {
                             if (j == 0 && w * SPAN + kWave <= nt) order_bad |= rank_check<8>(d, rk[j], a.rank_fault);
                         }
