@@ -1074,10 +1074,13 @@ def vendor_segmented_sort_device(keys_in, keys_out, offsets, ws=None, stream=Non
 
 def fingerprint(keys, vals=None, stream=None) -> tuple[int, int]:
     """rsort_fingerprint_device: (multiset fingerprint, adjacent descents) of keys (+ values)."""
-    out = torch.zeros(2, dtype=torch.int64, device=keys.device)
-    _check(_lib().rsort_fingerprint_device(_ptr(keys), _ptr(vals), keys.numel(), _ptr(out), _stream(stream)),
-           "rsort_fingerprint_device")
-    h, d = out.cpu().tolist()
+    _need_torch()
+    s = stream if stream is not None else torch.cuda.current_stream()
+    with torch.cuda.stream(s):  # the result buffer's fill and its read are ordered on the kernel's stream
+        out = torch.zeros(2, dtype=torch.int64, device=keys.device)
+        _check(_lib().rsort_fingerprint_device(_ptr(keys), _ptr(vals), keys.numel(), _ptr(out), s.cuda_stream),
+               "rsort_fingerprint_device")
+        h, d = out.cpu().tolist()
     return h & 0xFFFFFFFFFFFFFFFF, d
 
 

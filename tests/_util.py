@@ -155,5 +155,33 @@ def zipf_keys(n: int, seed: int = 0x5EED, ranks: int = 1 << 20, s: float = 1.0) 
     return fmix32(rank)
 
 
+# ----------------------------------------------------------------------------- output check
+def fmix64(k: np.ndarray) -> np.ndarray:
+    """MurmurHash3's 64-bit finalizer over a uint64 array."""
+    with np.errstate(over="ignore"):
+        k = k.astype(np.uint64)
+        k ^= k >> np.uint64(33)
+        k *= np.uint64(0xFF51AFD7ED558CCD)
+        k ^= k >> np.uint64(33)
+        k *= np.uint64(0xC4CEB9FE1A85EC53)
+        k ^= k >> np.uint64(33)
+        return k
+
+
+def fingerprint_ref(keys: np.ndarray, vals: np.ndarray | None = None) -> tuple[int, int]:
+    """Host statement of include/rsort.h "output check" (rsort_fingerprint_device): (h, descents) with
+    h = sum of fmix64(v << 32 | k) mod 2^64 (v = 0 without values) and descents = #{i : k[i] > k[i + 1]},
+    the keys compared as unsigned 32-bit numbers."""
+    k = np.ascontiguousarray(keys, dtype=np.uint32).astype(np.uint64)
+    word = k
+    if vals is not None:
+        v = np.ascontiguousarray(vals, dtype=np.uint32).astype(np.uint64)
+        assert v.size == k.size
+        word = (v << np.uint64(32)) | k
+    h = int(np.sum(fmix64(word), dtype=np.uint64))  # integer array sums wrap: the sum mod 2^64
+    descents = int(np.count_nonzero(k[:-1] > k[1:]))
+    return h, descents
+
+
 def env_flag(name: str) -> bool:
     return os.environ.get(name, "") not in ("", "0", "false", "False")
