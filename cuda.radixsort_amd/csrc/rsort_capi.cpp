@@ -943,6 +943,278 @@ int seg_host_sort(const uint32_t *kin, const uint32_t *vin, uint32_t *kout, uint
     return check ? RSORT_ERR_CHECK : RSORT_OK;
 }
 
+// ------------------------------------------------------------------------------ top-k selection
+// (rsort_topk.hip.) Workspace of rsort_u32_topk_device, by route; the state words come first on both, so
+// rsort_topk_report finds them without knowing the route. The caller's pointer may have any 4-byte alignment: the
+// regions start at its next multiple of 256 (the 256 B of slack in the formula).
+// AUTO selects for k <= n / kTopkAutoDiv[pairs] (rsort_topk_auto_limit). Measured (profiles/topk.json,
+// uniform keys at 2^26 and 2^30): keys only, SELECT is 1.30x faster than SORT at k = n / 16 at 2^30 and 8 % slower at
+// n / 4; with values or indices it is still 1.15x (2^26) and 1.20x (2^30) faster at k = n / 2, the largest k measured.
+constexpr int64_t kTopkAutoDiv[2] = {16, 2};
+
+struct TopkCarve {
+    uint32_t *state, *totals, *rows_cnt, *rows_pre, *offs0, *offs1, *wk, *wv, *ak, *av;  // SELECT
+    uint32_t *sk, *sv;                                                                   // SORT
+    void *sort_ws;
+    size_t sort_bytes, bytes;
+};
+
+// route: RSORT_TOPK_SELECT or RSORT_TOPK_SORT; plan: the finishing sort's (k entries) or the whole sort's (n)
+TopkCarve topk_carve(int64_t n, int64_t k, int pairs, int route, const rsort_plan &plan, void *ws) {
+    TopkCarve c{};
+    char *q = (char *)(((uintptr_t)ws + 255u) & ~(uintptr_t)255u);
+    size_t o = 0;
+    auto take = [&](size_t bytes) {
+        uint32_t *p = (uint32_t *)(q + o);
+        o += align256(bytes);
+        return p;
+    };
+    c.state = take(256);
+    if (route == RSORT_TOPK_SELECT) {
+        c.totals = take((size_t)kTopkTotalsWords * 4);
+        c.rows_cnt = take((size_t)kTopkMaxGrid * kTopkBins0 * 4);
+        c.rows_pre = take((size_t)kTopkMaxGrid * kTopkBins0 * 4);
+        c.offs0 = take((size_t)kTopkMaxGrid * 8);
+        c.offs1 = take((size_t)kTopkMaxGrid * 8);
+        c.wk = take((size_t)k * 4);
+        c.wv = pairs ? take((size_t)k * 4) : nullptr;
+        c.ak = take((size_t)n * 4);
+        c.av = pairs ? take((size_t)n * 4) : nullptr;
+    } else {
+        c.sk = take((size_t)n * 4);
+        c.sv = pairs ? take((size_t)n * 4) : nullptr;
+    }
+    c.sort_ws = q + o;
+    c.sort_bytes = plan.workspace_bytes;
+    c.bytes = o + c.sort_bytes + 256;
+    return c;
+}
+
+std::atomic<int> g_topk_route{RSORT_TOPK_AUTO};
+std::atomic<int> g_topk_grid_limit{0};  // rsort_set_topk_grid_limit (tests); 0: no limit
+
+constexpr int kTopkFlags = RSORT_TOPK_LARGEST | RSORT_TOPK_UNSORTED | RSORT_TOPK_INDICES;
+
+bool topk_sizes_ok(int64_t n, int64_t k, int *st) {
+    *st = RSORT_OK;
+    if (n < 0 || n >= ((int64_t)1 << 32)) *st = RSORT_ERR_SIZE;
+    else if (k < 0 || k > n) *st = RSORT_ERR_ARG;
+    return *st == RSORT_OK;
+}
+
+int64_t topk_auto_limit(int64_t n, int pairs) { return n / kTopkAutoDiv[pairs ? 1 : 0]; }
+
+// `route` as given (AUTO, SELECT, SORT) -> the route a call for (n, k) takes
+int topk_resolve(int route, int64_t n, int64_t k, int pairs) {
+    if (route != RSORT_TOPK_AUTO) return route;
+    return k <= topk_auto_limit(n, pairs) ? RSORT_TOPK_SELECT : RSORT_TOPK_SORT;
+}
+
+// The finishing sort's plan (k entries) on SELECT, the whole sort's (n) on SORT.
+int topk_plan(int64_t n, int64_t k, int pairs, int route, rsort_plan *p) {
+    return plan_fill(route == RSORT_TOPK_SELECT ? k : n, 8, pairs, 0, p);
+}
+
+// G, the workgroups of every select kernel of one call (the launches and rsort_topk_grids share it): what the
+// device holds at once, at most one workgroup per tile of the input but never fewer than 64 (the candidate list's
+// kernels run on the same grid), capped by the picks' one-slice-per-thread limit and by the test hook.
+uint32_t topk_grid(int64_t n) {
+    const int64_t cus = std::max(1, device_cus()), bpc = std::max(1, topk_blocks_per_cu());
+    const int64_t tiles = (n + kTopkTile - 1) / kTopkTile;
+    int64_t g = std::min<int64_t>({cus * bpc, (int64_t)kTopkMaxGrid, std::max<int64_t>(64, tiles)});
+    const int limit = g_topk_grid_limit.load();
+    if (limit > 0) g = std::min<int64_t>(g, limit);
+    return (uint32_t)g;
+}
+
+// The argument checks the device and the host entry share; *noop: nothing to do (k == 0).
+int topk_check(const void *kin, const void *vin, int64_t n, int64_t k, int flags, const void *kout, const void *vout,
+               bool *noop) {
+    int st;
+    *noop = false;
+    if (!topk_sizes_ok(n, k, &st)) return st;
+    if (flags & ~kTopkFlags) return RSORT_ERR_ARG;
+    if (flags & RSORT_TOPK_INDICES) {
+        if (vin != nullptr) return RSORT_ERR_ARG;
+    } else if ((vin != nullptr) != (vout != nullptr)) {
+        return RSORT_ERR_ARG;
+    }
+    if (k == 0) {
+        *noop = true;
+        return RSORT_OK;
+    }
+    if ((flags & RSORT_TOPK_INDICES) && vout == nullptr) return RSORT_ERR_ARG;
+    if (!kin || !kout) return RSORT_ERR_ARG;
+    return RSORT_OK;
+}
+
+int topk_select(const uint32_t *kin, const uint32_t *vin, int64_t n, int64_t k, int flags, uint32_t *kout,
+                uint32_t *vout, const TopkCarve &c, const rsort_plan &plan, hipStream_t s) {
+    const int pairs = vout != nullptr;
+    const uint32_t m = (flags & RSORT_TOPK_LARGEST) ? 0xFFFFFFFFu : 0u;
+    const uint32_t grid = topk_grid(n);
+    TopkArgs a{};
+    a.kin = kin;
+    a.vin = vin;
+    a.state = c.state;
+    a.totals = c.totals;
+    a.rows_cnt = c.rows_cnt;
+    a.rows_pre = c.rows_pre;
+    a.offs0 = c.offs0;
+    a.offs1 = c.offs1;
+    a.wk = c.wk;
+    a.wv = c.wv;
+    a.ak = c.ak;
+    a.av = c.av;
+    a.n = (uint64_t)n;
+    a.k = (uint32_t)k;
+    a.m = m;
+    a.pairs = pairs ? 1u : 0u;
+    a.indices = (flags & RSORT_TOPK_INDICES) ? 1u : 0u;
+    a.vec = (((uintptr_t)kin & 15u) == 0) ? 1u : 0u;
+    int st;
+    // the state words and the three levels' totals are adjacent: one memset node
+    if (hipMemsetAsync(c.state, 0, 256 + align256((size_t)kTopkTotalsWords * 4), s) != hipSuccess) return RSORT_ERR_HIP;
+    auto count = [&](int level, int64_t keys) {
+        PhaseScope ps(RSORT_PHASE_HISTOGRAM, keys, s);
+        return hip_status(launch_topk_count(level, a, grid, s));
+    };
+    auto pick = [&](int level) {
+        PhaseScope ps(RSORT_PHASE_SCAN, level == 0 ? kTopkBins0 : kTopkBins, s);
+        return hip_status(launch_topk_pick(level, a, grid, s));
+    };
+    if ((st = count(0, n)) || (st = pick(0))) return st;
+    {
+        PhaseScope ps(RSORT_PHASE_SCATTER, n, s);
+        if ((st = hip_status(launch_topk_compact(a, grid, s)))) return st;
+    }
+    // (the candidate list's length is the device's: the profile counts no keys for its kernels)
+    if ((st = count(1, 0)) || (st = pick(1)) || (st = count(2, 0)) || (st = pick(2))) return st;
+    {
+        PhaseScope ps(RSORT_PHASE_HISTOGRAM, 0, s);
+        if ((st = hip_status(launch_topk_tie_count(a, grid, s)))) return st;
+    }
+    {
+        PhaseScope ps(RSORT_PHASE_SCATTER, 0, s);
+        if ((st = hip_status(launch_topk_emit(a, grid, s)))) return st;
+    }
+    // W holds the k entries as x = key ^ m, equal keys in input order
+    TopkCopyArgs cp{};
+    cp.kout = kout;
+    cp.n = cp.k = (uint64_t)k;
+    cp.m = m;
+    if (flags & RSORT_TOPK_UNSORTED) {
+        cp.kin = c.wk;
+        cp.vin = c.wv;
+        cp.vout = vout;
+    } else {
+        if ((st = sort_planned(plan, c.wk, c.wv, kout, vout, c.sort_ws, c.sort_bytes, s))) return st;
+        if (m == 0) return RSORT_OK;
+        cp.kin = kout;  // the sorted x back to keys, in place
+    }
+    PhaseScope ps(RSORT_PHASE_COPY, k, s);
+    return hip_status(launch_topk_copy(cp, s));
+}
+
+// The whole sort and a slice: what a caller without the select does. The sorted arrays (n entries) live in the
+// workspace. Keys only: the input is sorted as it is and the k largest are its last k, reversed. With values or
+// indices the sort must be stable in x = key ^ m, so LARGEST sorts a transformed copy; INDICES sorts an iota array.
+int topk_sort(const uint32_t *kin, const uint32_t *vin, int64_t n, int64_t k, int flags, uint32_t *kout,
+              uint32_t *vout, const TopkCarve &c, const rsort_plan &plan, hipStream_t s) {
+    const bool pairs = vout != nullptr, largest = (flags & RSORT_TOPK_LARGEST) != 0;
+    int st;
+    if (hipMemsetAsync(c.state, 0xFF, 256, s) != hipSuccess) return RSORT_ERR_HIP;
+    const uint32_t *ks = kin, *vs = vin;
+    if (pairs && largest) {
+        PhaseScope ps(RSORT_PHASE_COPY, n, s);
+        TopkCopyArgs x{};
+        x.kin = kin;
+        x.kout = c.sk;
+        x.n = x.k = (uint64_t)n;
+        x.m = 0xFFFFFFFFu;
+        if ((st = hip_status(launch_topk_copy(x, s)))) return st;
+        ks = c.sk;
+    }
+    if (flags & RSORT_TOPK_INDICES) {
+        PhaseScope ps(RSORT_PHASE_COPY, n, s);
+        if ((st = hip_status(launch_gen_iota(c.sv, (uint64_t)n, 0, s)))) return st;
+        vs = c.sv;
+    }
+    if ((st = sort_planned(plan, ks, vs, c.sk, c.sv, c.sort_ws, c.sort_bytes, s))) return st;
+    TopkCopyArgs cp{};
+    cp.kin = c.sk;
+    cp.vin = c.sv;
+    cp.kout = kout;
+    cp.vout = vout;
+    cp.state = c.state;
+    cp.n = (uint64_t)n;
+    cp.k = (uint64_t)k;
+    cp.m = (pairs && largest) ? 0xFFFFFFFFu : 0u;
+    cp.rev = (!pairs && largest) ? 1u : 0u;
+    PhaseScope ps(RSORT_PHASE_COPY, k, s);
+    return hip_status(launch_topk_copy(cp, s));
+}
+
+int topk_device(const uint32_t *kin, const uint32_t *vin, int64_t n, int64_t k, int flags, uint32_t *kout,
+                uint32_t *vout, void *ws, size_t ws_bytes, hipStream_t s) {
+    bool noop;
+    int st = topk_check(kin, vin, n, k, flags, kout, vout, &noop);
+    if (st || noop) return st;
+    if (!ws) return RSORT_ERR_ARG;
+    if (!aligned4(kin) || !aligned4(vin) || !aligned4(kout) || !aligned4(vout) || !aligned4(ws)) return RSORT_ERR_ALIGN;
+    const int pairs = vout != nullptr;
+    const int route = topk_resolve(g_topk_route.load(), n, k, pairs);
+    rsort_plan plan;
+    if ((st = topk_plan(n, k, pairs, route, &plan))) return st;
+    const TopkCarve c = topk_carve(n, k, pairs, route, plan, ws);
+    if (ws_bytes < c.bytes) return RSORT_ERR_WORKSPACE;
+    return route == RSORT_TOPK_SELECT ? topk_select(kin, vin, n, k, flags, kout, vout, c, plan, s)
+                                      : topk_sort(kin, vin, n, k, flags, kout, vout, c, plan, s);
+}
+
+size_t topk_workspace_size(int64_t n, int64_t k, int pairs, int route) {
+    int st;
+    if (!topk_sizes_ok(n, k, &st) || route < RSORT_TOPK_AUTO || route > RSORT_TOPK_SORT) return 0;
+    route = topk_resolve(route, n, k, pairs);
+    rsort_plan plan;
+    if (topk_plan(n, k, pairs, route, &plan)) return 0;
+    return topk_carve(n, k, pairs, route, plan, nullptr).bytes;
+}
+
+int topk_host(const uint32_t *kin, const uint32_t *vin, int64_t n, int64_t k, int flags, uint32_t *kout,
+              uint32_t *vout) {
+    bool noop;
+    int st = topk_check(kin, vin, n, k, flags, kout, vout, &noop);
+    if (st || noop) return st;
+    const int pairs = vout != nullptr;
+    int count = 0, dev = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return RSORT_ERR_NODEV;
+    if (hipGetDevice(&dev) != hipSuccess) return RSORT_ERR_HIP;
+    DevCache *dc = cache_for(dev);
+    std::lock_guard<std::mutex> g(dc->mu);
+    const size_t nb = align256((size_t)n * 4), kb = align256((size_t)k * 4);
+    const size_t wsb = topk_workspace_size(n, k, pairs, g_topk_route.load());
+    if ((st = dc->reserve(2 * nb + 2 * kb + wsb))) return st;
+    char *q = (char *)dc->buf;
+    uint32_t *d_kin = (uint32_t *)q;
+    uint32_t *d_vin = vin ? (uint32_t *)(q + nb) : nullptr;
+    uint32_t *d_kout = (uint32_t *)(q + 2 * nb);
+    uint32_t *d_vout = pairs ? (uint32_t *)(q + 2 * nb + kb) : nullptr;
+    void *ws = q + 2 * nb + 2 * kb;
+    hipStream_t s = dc->stream;
+    if (hipMemcpyAsync(d_kin, kin, (size_t)n * 4, hipMemcpyHostToDevice, s) != hipSuccess) return RSORT_ERR_HIP;
+    if (vin && hipMemcpyAsync(d_vin, vin, (size_t)n * 4, hipMemcpyHostToDevice, s) != hipSuccess) return RSORT_ERR_HIP;
+    st = topk_device(d_kin, d_vin, n, k, flags, d_kout, d_vout, ws, wsb, s);
+    if (st) {
+        (void)hipStreamSynchronize(s);
+        return st;
+    }
+    if (hipMemcpyAsync(kout, d_kout, (size_t)k * 4, hipMemcpyDeviceToHost, s) != hipSuccess) return RSORT_ERR_HIP;
+    if (pairs && hipMemcpyAsync(vout, d_vout, (size_t)k * 4, hipMemcpyDeviceToHost, s) != hipSuccess)
+        return RSORT_ERR_HIP;
+    return hip_status(hipStreamSynchronize(s));
+}
+
 }  // namespace
 
 void rsort::profile_pause(int delta) { t_prof_paused += delta; }
@@ -1094,6 +1366,73 @@ int rsort_set_segmented_grid_limit(int workgroups) {
 int rsort_u32_segmented(const uint32_t *keys_in, const uint32_t *vals_in, uint32_t *keys_out, uint32_t *vals_out,
                         int64_t n, const uint32_t *offsets, int64_t num_segments) {
     return seg_host_sort(keys_in, vals_in, keys_out, vals_out, n, offsets, num_segments);
+}
+
+size_t rsort_topk_workspace_size(int64_t n, int64_t k, int pairs, int route) {
+    return topk_workspace_size(n, k, pairs ? 1 : 0, route);
+}
+
+int rsort_u32_topk_device(const uint32_t *d_keys_in, const uint32_t *d_vals_in, int64_t n, int64_t k, int flags,
+                          uint32_t *d_keys_out, uint32_t *d_vals_out, void *d_workspace, size_t workspace_bytes,
+                          void *stream) {
+    return topk_device(d_keys_in, d_vals_in, n, k, flags, d_keys_out, d_vals_out, d_workspace, workspace_bytes,
+                       (hipStream_t)stream);
+}
+
+int rsort_u32_topk(const uint32_t *keys, const uint32_t *vals, int64_t n, int64_t k, int flags, uint32_t *keys_out,
+                   uint32_t *vals_out) {
+    return topk_host(keys, vals, n, k, flags, keys_out, vals_out);
+}
+
+int rsort_topk_report(int64_t n, int64_t k, int pairs, const void *d_workspace, int64_t *report8, void *stream) {
+    int st;
+    (void)pairs;  // (the state words come first in the workspace whatever the layout behind them)
+    if (!report8) return RSORT_ERR_ARG;
+    for (int i = 0; i < 8; ++i) report8[i] = 0;
+    if (!topk_sizes_ok(n, k, &st)) return st;
+    if (k == 0) return RSORT_OK;
+    if (!d_workspace) return RSORT_ERR_ARG;
+    const rsort_plan none{};
+    const TopkCarve c = topk_carve(0, 0, 0, RSORT_TOPK_SORT, none, const_cast<void *>(d_workspace));
+    uint32_t h[8] = {0};
+    if ((st = read_words(h, c.state, 8, (hipStream_t)stream))) return st;
+    const bool sorted = h[kTkRoute] == (uint32_t)RSORT_TOPK_SORT;
+    for (int i = 0; i < 6; ++i) report8[i] = (sorted && i >= 2) ? -1 : (int64_t)h[i];
+    return RSORT_OK;
+}
+
+int rsort_set_topk_route(int route) {
+    if (route < RSORT_TOPK_AUTO || route > RSORT_TOPK_SORT) return -RSORT_ERR_ARG;
+    return g_topk_route.exchange(route);
+}
+
+int rsort_get_topk_route(void) { return g_topk_route.load(); }
+
+int rsort_topk_auto_limit(int64_t n, int pairs, int64_t *k_max) {
+    if (!k_max) return RSORT_ERR_ARG;
+    *k_max = 0;
+    if (n < 0 || n >= ((int64_t)1 << 32)) return RSORT_ERR_SIZE;
+    *k_max = topk_auto_limit(n, pairs ? 1 : 0);
+    return RSORT_OK;
+}
+
+int rsort_topk_grids(int64_t n, int64_t k, int pairs, int *grids) {
+    int st;
+    (void)pairs;  // (keys and pairs run the same kernels)
+    if (!grids) return RSORT_ERR_ARG;
+    for (int i = 0; i < 4; ++i) grids[i] = 0;
+    if (!topk_sizes_ok(n, k, &st)) return st;
+    if (k == 0) return RSORT_OK;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return RSORT_ERR_NODEV;
+    const int g = (int)topk_grid(n);
+    for (int i = 0; i < 4; ++i) grids[i] = g;
+    return RSORT_OK;
+}
+
+int rsort_set_topk_grid_limit(int workgroups) {
+    if (workgroups < 0) return -RSORT_ERR_ARG;
+    return g_topk_grid_limit.exchange(workgroups);
 }
 
 int rsort_pass_histogram(const rsort_plan *plan, const uint32_t *d_keys, int shift,

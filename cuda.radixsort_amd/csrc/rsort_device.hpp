@@ -1,5 +1,5 @@
 // rsort_device.hpp -- device helpers shared by the kernel translation units (rsort_kernels.hip,
-// rsort_segmented.hip): lane and wave primitives, the lane-ordered and ballot rankings with their rank
+// rsort_segmented.hip, rsort_topk.hip): lane and wave primitives, the lane-ordered and ballot rankings with their rank
 // check, and the wave / workgroup scans. Device code only; every function is inline.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,4 +1,4 @@
-// rsort_internal.hpp -- shared between the HIP kernels (rsort_kernels.hip, rsort_segmented.hip) and
+// rsort_internal.hpp -- shared between the HIP kernels (rsort_kernels.hip, rsort_segmented.hip, rsort_topk.hip) and
 // the host driver (rsort_capi.cpp). Not part of the public ABI (include/rsort.h is).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -400,6 +400,50 @@ hipError_t launch_seg_classify(const SegClassifyArgs &a, hipStream_t s);
 hipError_t launch_seg_sort(int kind, int pairs, int rank_algo, const SegSortArgs &a, uint32_t grid, hipStream_t s);
 // Resident workgroups per CU of a segmented-sort kernel (occupancy query), 0 on error.
 int seg_blocks_per_cu(int kind, int pairs, int rank_algo);
+// ------------------------------------------------------------------------------ top-k selection
+// (rsort_topk.hip; rsort_u32_topk_device.) A radix select over x = key ^ m (m = ~0 for the k largest): three
+// levels of 8 / 12 / 12 bits from the top. Every kernel but the picks runs on G workgroups of kTopkThreads
+// threads; workgroup g owns a contiguous slice of whole kTopkTile-key tiles of its list, whose length (n, or the
+// device-side candidate count) it reads itself. Level 0 reads the input twice (count, compact): the entries
+// below the chosen top digit go to W, those with it to the candidate list A. Levels 1 and 2 count over A; then the
+// k-th x, T, is known and one count + one emit over A append x < T and the first k_rem entries x == T to W.
+constexpr int kTopkThreads = 1024, kTopkKpt = 4;
+constexpr int kTopkTile = kTopkThreads * kTopkKpt;
+constexpr uint32_t kTopkMaxGrid = 1024;           // G <= this: the picks handle one slice per thread
+constexpr uint32_t kTopkBins0 = 256, kTopkBins = 4096;
+constexpr uint32_t kTopkTotalsWords = kTopkBins0 + 2 * kTopkBins;  // the bin totals of levels 0, 1, 2
+// The call's 256 B of state, first in the workspace (rsort_topk_report reads words 0..7). A SELECT call clears
+// it with the totals; a SORT call fills it with ~0 and writes the route, the k-th key and the reserved words.
+enum TopkWord : uint32_t { kTkRoute = 0, kTkKth = 1, kTkBefore = 2, kTkTaken = 3, kTkEqual = 4, kTkCand = 5,
+                           kTkKrem = 8, kTkPrefix = 9, kTkBelow0 = 10, kTkWords = 64 };
+struct TopkArgs {
+    const uint32_t *kin, *vin;   // the input (vin == nullptr: keys only, or indices)
+    uint32_t *state, *totals;
+    uint32_t *rows_cnt, *rows_pre;  // level 0: [slice][top digit] counts and their exclusive prefix over the digits
+    uint32_t *offs0, *offs1;        // per slice {below, equal}: level 0's exclusive offsets; the tie counts
+    uint32_t *wk, *wv, *ak, *av;    // W (k entries), A (up to n)
+    uint64_t n;
+    uint32_t k, m;
+    uint32_t pairs, indices, vec;   // vec: kin is 16-byte aligned
+};
+// level 0..2; grid workgroups (<= kTopkMaxGrid), the same for every launch of one call
+hipError_t launch_topk_count(int level, const TopkArgs &a, uint32_t grid, hipStream_t s);
+hipError_t launch_topk_pick(int level, const TopkArgs &a, uint32_t grid, hipStream_t s);
+hipError_t launch_topk_compact(const TopkArgs &a, uint32_t grid, hipStream_t s);
+hipError_t launch_topk_tie_count(const TopkArgs &a, uint32_t grid, hipStream_t s);
+hipError_t launch_topk_emit(const TopkArgs &a, uint32_t grid, hipStream_t s);
+// kout[i] = kin[rev ? n - 1 - i : i] ^ m (and vout[i] = vin[i]) for i < k; kin == kout is allowed when !rev.
+// state != nullptr: the SORT route's report words (the route, the k-th key = kout[k - 1], the reserved zeros).
+struct TopkCopyArgs {
+    const uint32_t *kin, *vin;
+    uint32_t *kout, *vout, *state;
+    uint64_t n, k;
+    uint32_t m, rev;
+};
+hipError_t launch_topk_copy(const TopkCopyArgs &a, hipStream_t s);
+// Fewest resident workgroups per CU over the select kernels (occupancy query), 0 on error.
+int topk_blocks_per_cu();
+
 // Raw next-digit tables (every workgroup of a pass sums the whole R x C table for its own starts) cost
 // O(R x C) reads per workgroup, O(R x C^2) per pass: only plans of at most this many chunks (about one
 // resident wave: C2 has 1024) take them; larger ones keep the tail scan (DESIGN §8 measured

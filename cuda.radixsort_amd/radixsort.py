@@ -240,6 +240,15 @@ SIGNATURES = {
     "rsort_u32_segmented": ([_vp, _vp, _vp, _vp, _i64, _vp, _i64], _int),
     "rsort_segmented_grids": ([_i64, _i64, _int, ctypes.POINTER(_int)], _int),
     "rsort_set_segmented_grid_limit": ([_int], _int),
+    "rsort_topk_workspace_size": ([_i64, _i64, _int, _int], _sz),
+    "rsort_u32_topk_device": ([_vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _sz, _vp], _int),
+    "rsort_u32_topk": ([_vp, _vp, _i64, _i64, _int, _vp, _vp], _int),
+    "rsort_topk_report": ([_i64, _i64, _int, _vp, ctypes.POINTER(_i64), _vp], _int),
+    "rsort_set_topk_route": ([_int], _int),
+    "rsort_get_topk_route": ([], _int),
+    "rsort_topk_auto_limit": ([_i64, _int, ctypes.POINTER(_i64)], _int),
+    "rsort_topk_grids": ([_i64, _i64, _int, ctypes.POINTER(_int)], _int),
+    "rsort_set_topk_grid_limit": ([_int], _int),
     "rsort_vendor_segmented_workspace_size": ([_i64, _i64], _sz),
     "rsort_u32_vendor_segmented_device": ([_vp, _vp, _i64, _vp, _i64, _vp, _sz, _vp], _int),
     "rsort_fingerprint_device": ([_vp, _vp, _i64, _vp, _vp], _int),
@@ -1070,6 +1079,109 @@ def vendor_segmented_sort_device(keys_in, keys_out, offsets, ws=None, stream=Non
     _check(_lib().rsort_u32_vendor_segmented_device(_ptr(keys_in), _ptr(keys_out), n, _ptr(off), nseg, _ptr(ws),
                                                     ws.numel(), _stream(stream)), "rsort_u32_vendor_segmented_device")
     return off, ws
+
+
+# ---------------------------------------------------------------- top-k selection
+TOPK_LARGEST, TOPK_UNSORTED, TOPK_INDICES = 1, 2, 4
+TOPK_AUTO, TOPK_SELECT, TOPK_SORT = 0, 1, 2
+TOPK_TILE_KEYS = 4096  # entries per tile of the select kernels (include/rsort.h)
+TOPK_REPORT = ("route", "kth_key", "before", "equal_taken", "equal_in_input", "candidates")
+
+
+def _topk_flags(largest, indices, sorted):
+    return (TOPK_LARGEST if largest else 0) | (TOPK_INDICES if indices else 0) | (0 if sorted else TOPK_UNSORTED)
+
+
+def topk_workspace_size(n: int, k: int, pairs: bool = False, route: int = TOPK_AUTO) -> int:
+    """rsort_topk_workspace_size: with a route forced (topk_route) pass that route."""
+    return int(_lib().rsort_topk_workspace_size(int(n), int(k), 1 if pairs else 0, int(route)))
+
+
+def get_topk_route() -> int:
+    return int(_lib().rsort_get_topk_route())
+
+
+@contextmanager
+def topk_route(mode: int):
+    """rsort_set_topk_route (process-wide) for the block: TOPK_AUTO, TOPK_SELECT or TOPK_SORT."""
+    old = int(_lib().rsort_set_topk_route(int(mode)))
+    if old < 0:
+        raise RSortError(-old, "rsort_set_topk_route")
+    try:
+        yield
+    finally:
+        _lib().rsort_set_topk_route(old)
+
+
+def topk_auto_limit(n: int, pairs: bool = False) -> int:
+    """rsort_topk_auto_limit: TOPK_AUTO selects for k up to this, and sorts above."""
+    v = _i64()
+    _check(_lib().rsort_topk_auto_limit(int(n), 1 if pairs else 0, ctypes.byref(v)), "rsort_topk_auto_limit")
+    return int(v.value)
+
+
+TOPK_KERNELS = ("count", "compact", "tie_count", "emit")
+
+
+def topk_grids(n: int, k: int, pairs: bool = False) -> dict:
+    """rsort_topk_grids: the workgroups each select kernel of a call with these arguments is launched with now."""
+    g = (ctypes.c_int * 4)()
+    _check(_lib().rsort_topk_grids(int(n), int(k), 1 if pairs else 0, g), "rsort_topk_grids")
+    return {name: int(g[i]) for i, name in enumerate(TOPK_KERNELS)}
+
+
+@contextmanager
+def topk_grid_limit(workgroups: int):
+    """TEST HOOK (rsort_set_topk_grid_limit): every select kernel runs with at most `workgroups` workgroups, so
+    each walks several tiles; the previous setting comes back on exit."""
+    old = int(_lib().rsort_set_topk_grid_limit(int(workgroups)))
+    if old < 0:
+        raise RSortError(-old, "rsort_set_topk_grid_limit")
+    try:
+        yield
+    finally:
+        _lib().rsort_set_topk_grid_limit(old)
+
+
+def topk_device(keys, k, largest=False, vals=None, indices=False, sorted=True, out=None, ws=None, stream=None):
+    """rsort_u32_topk_device: the k smallest (largest=True: largest) keys of a torch int32 tensor (bits = u32
+    keys), with their values (vals) or input positions (indices=True); stream-ordered. out: (keys_out, vals_out or
+    None) of k elements each. Returns (keys_out, vals_out or None, workspace) -- what topk_report needs."""
+    n, k = keys.numel(), int(k)
+    pairs = vals is not None or indices
+    if out is None:
+        out = (empty_u32(k, keys.device), empty_u32(k, keys.device) if pairs else None)
+    kout, vout = out
+    if ws is None:
+        ws = workspace(topk_workspace_size(n, k, pairs, get_topk_route()), keys.device)
+    _check(_lib().rsort_u32_topk_device(_ptr(keys), _ptr(vals), n, k, _topk_flags(largest, indices, sorted),
+                                        _ptr(kout), _ptr(vout), _ptr(ws), ws.numel(), _stream(stream)),
+           "rsort_u32_topk_device")
+    return kout, vout, ws
+
+
+def topk_report(n: int, k: int, pairs: bool, ws, stream=None) -> dict:
+    """rsort_topk_report of the last top-k call in `ws` (synchronises the stream): {route, kth_key, before,
+    equal_taken, equal_in_input, candidates}; on the SORT route the last four are -1."""
+    r = (ctypes.c_int64 * 8)()
+    _check(_lib().rsort_topk_report(int(n), int(k), 1 if pairs else 0, _ptr(ws), r, _stream(stream)),
+           "rsort_topk_report")
+    return {name: int(r[i]) for i, name in enumerate(TOPK_REPORT)}
+
+
+def topkByDevice(keys, k, largest=False, vals=None, indices=False, sorted=True):
+    """rsort_u32_topk over numpy host arrays: (keys_out, vals_out or None) of k elements. Synchronous."""
+    keys = _host_u32(keys, None, "keys")
+    n, k = keys.size, int(k)
+    if vals is not None:
+        vals = _host_u32(vals, n, "vals")
+    pairs = vals is not None or indices
+    kout = np.empty(max(k, 0), np.uint32)
+    vout = np.empty(max(k, 0), np.uint32) if pairs else None
+    _check(_lib().rsort_u32_topk(keys.ctypes.data, vals.ctypes.data if vals is not None else None, n, k,
+                                 _topk_flags(largest, indices, sorted), kout.ctypes.data,
+                                 vout.ctypes.data if pairs else None), "topkByDevice")
+    return kout, vout
 
 
 def fingerprint(keys, vals=None, stream=None) -> tuple[int, int]:

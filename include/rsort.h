@@ -19,6 +19,7 @@
  *   rsort_u32_vendor     sortByThrust (the vendor comparator)                 Parallel7.cu:69-73
  *   (no counterpart)     rsort_u32_pairs*: key + u32 payload (BASELINE config 4)
  *   (no counterpart)     rsort_u32_segmented*: many independent segments of one array in one call
+ *   (no counterpart)     rsort_u32_topk*: the k smallest or largest keys and their input positions
  *   (no counterpart)     rsort_partition_device / rsort_bucket_starts: the multi-GPU
  *                        key-range partition step (BASELINE config 5)
  *
@@ -224,6 +225,89 @@ RSORT_API int    rsort_segmented_check(int64_t n, int64_t num_segments, int pair
 RSORT_API int    rsort_u32_segmented(const uint32_t *keys_in, const uint32_t *vals_in, uint32_t *keys_out,
                                      uint32_t *vals_out, int64_t n, const uint32_t *offsets,
                                      int64_t num_segments);
+
+/* ---------------------------------------------------------------- top-k selection */
+/* The k smallest or largest keys of n, and where they sit in the input, without sorting all n (no reference
+ * counterpart; what a caller otherwise does with rsort_u32_pairs_device over an iota array and a slice).
+ *   - Result, unique: let m = 0xFFFFFFFF with RSORT_TOPK_LARGEST, else 0. Take the STABLE ascending sort of the
+ *     entries by key ^ m (equal keys stay in input order); the output is its first k entries, keys_out[0..k) and
+ *     vals_out[0..k). So the smallest come smallest first and the largest come largest first; among the keys equal
+ *     to the k-th key those at the lowest input positions are taken, and stay in input order. A keys-only result
+ *     is simply the sorted multiset. With RSORT_TOPK_UNSORTED the same k (key, value) entries come back in an
+ *     unspecified order.
+ *   - Values: d_vals_in / d_vals_out both given: each key's u32 payload travels with it. RSORT_TOPK_INDICES:
+ *     d_vals_in must be NULL and d_vals_out receives each key's position in the input (no iota array is read).
+ *     `pairs` in the size, report and grid functions means "values or INDICES".
+ *   - Limits: 0 <= n < 2^32, 0 <= k <= n; k == 0 (so also n == 0) is a no-op that needs no buffers.
+ *   - Buffers: any 4-byte alignment (keys, values, outputs, workspace). The outputs must not overlap the inputs;
+ *     the inputs are never written. Stream-ordered on `stream`, no allocation, no host synchronisation,
+ *     graph-capturable; the current device; the workspace's content on entry is arbitrary.
+ *   - Routes (rsort_set_topk_route, process-wide): RSORT_TOPK_SELECT, a radix select -- two reads of the input
+ *     (the top 8 bits of key ^ m are counted per slice, then the entries below the digit that holds the k-th go to
+ *     the result and those with it to a candidate list), two more counts over the candidates (12 bits each), after
+ *     which the k-th key is known exactly, one count and one append over the candidates, and rsort_sort_planned of
+ *     the k entries. Every kernel runs on a host-known grid (rsort_topk_grids) of 1024-thread workgroups over
+ *     tiles of 4096 entries; the candidate list's length stays on the device. RSORT_TOPK_SORT: the whole sort of
+ *     the n entries (of an iota array with INDICES, of a transformed copy with LARGEST and values) and a copy of
+ *     the first k: what a caller without the select does; same contract, bit-identical output. RSORT_TOPK_AUTO
+ *     (default): SELECT for k <= rsort_topk_auto_limit(n, pairs), else SORT.
+ *   - Workspace bytes (rsort_topk_workspace_size; with a route forced pass that route, with RSORT_TOPK_AUTO it is
+ *     what the automatic route for (n, k) needs), with r(x) = x rounded up to a multiple of 256 and p = pairs ? 2 : 1:
+ *       SELECT:   256                      the state and report words
+ *               + r(4 * 8448)              the bin totals of the three levels (256 + 4096 + 4096)
+ *               + 2 * 1024 * 256 * 4       the per-slice digit counts of level 0 and their prefixes (up to 1024 slices)
+ *               + 2 * r(8 * 1024)          the per-slice offsets of level 0 and of the last step
+ *               + p * r(4 k)               the selected entries
+ *               + p * r(4 n)               the candidates (all n when the top digit separates nothing)
+ *               + rsort_workspace_size(k, 8, pairs)   the finishing sort
+ *               + 256                      alignment slack
+ *       SORT:     256 + p * r(4 n) + rsort_workspace_size(n, 8, pairs) + 256
+ *   - Errors, returned before any HIP call: RSORT_ERR_SIZE (n), RSORT_ERR_ARG (k out of range, unknown flag bits,
+ *     exactly one of the two value pointers, INDICES with a non-NULL d_vals_in or a NULL d_vals_out, NULL keys /
+ *     output / workspace), RSORT_ERR_ALIGN, RSORT_ERR_WORKSPACE.
+ *   - rsort_profile_begin/end: the counts are RSORT_PHASE_HISTOGRAM, the picks RSORT_PHASE_SCAN, the compaction and
+ *     the append RSORT_PHASE_SCATTER, the copies RSORT_PHASE_COPY; the finishing sort reports its own phases. */
+#define RSORT_TOPK_LARGEST  1   /* the k largest instead of the k smallest */
+#define RSORT_TOPK_UNSORTED 2   /* the same k entries, in no particular order */
+#define RSORT_TOPK_INDICES  4   /* d_vals_in must be NULL; d_vals_out receives each key's input position */
+
+#define RSORT_TOPK_AUTO 0
+#define RSORT_TOPK_SELECT 1
+#define RSORT_TOPK_SORT 2
+
+RSORT_API size_t rsort_topk_workspace_size(int64_t n, int64_t k, int pairs, int route);
+RSORT_API int    rsort_u32_topk_device(const uint32_t *d_keys_in, const uint32_t *d_vals_in, int64_t n, int64_t k,
+                                       int flags, uint32_t *d_keys_out, uint32_t *d_vals_out, void *d_workspace,
+                                       size_t workspace_bytes, void *stream);
+/* host -> host, synchronous, library-owned cached workspace (as rsort_u32). RSORT_ERR_NODEV without a device. */
+RSORT_API int    rsort_u32_topk(const uint32_t *keys, const uint32_t *vals, int64_t n, int64_t k, int flags,
+                                uint32_t *keys_out, uint32_t *vals_out);
+/* After the call has completed on `stream` in `d_workspace`: report8[0] = the route taken (RSORT_TOPK_SELECT or
+ * RSORT_TOPK_SORT), [1] = the k-th key (as stored, not xor-ed), [2] = the selected entries strictly before it in
+ * the order, [3] = the entries equal to it that were taken, [4] = the entries equal to it in the input, [5] = the
+ * candidates left after the first digit, [6], [7] = 0 (reserved). On the SORT route [0] and [1] are filled and
+ * [2..5] are -1. All 0 for k == 0. Synchronises the stream, as rsort_segmented_check does. */
+RSORT_API int    rsort_topk_report(int64_t n, int64_t k, int pairs, const void *d_workspace, int64_t *report8,
+                                   void *stream);
+/* Process-wide, like rsort_set_hybrid; returns the old route, or -RSORT_ERR_ARG for an unknown one (nothing changes). */
+RSORT_API int    rsort_set_topk_route(int route);
+RSORT_API int    rsort_get_topk_route(void);
+/* RSORT_TOPK_AUTO selects for k <= *k_max: n / 16 keys only, n / 2 with values or indices. From the uniform-key rows
+ * of profiles/topk.json, the largest measured k / n at which SELECT beat SORT at both 2^26 and 2^30 keys:
+ * keys only 1.30x at n / 16 (2^30; n / 4 is 8 % slower there), pairs 1.15x and 1.20x at n / 2, the largest k measured --
+ * margins many times the ~1 % run-to-run spread. Keys whose top digit separates nothing (all below 2^24, say) make
+ * SELECT read everything five times: keys only it is then 17 % (small k) to 27 % (k = n / 16) slower than SORT at 2^30
+ * keys, and still ahead with values or indices; AUTO cannot know the keys before it reads them. */
+RSORT_API int    rsort_topk_auto_limit(int64_t n, int pairs, int64_t *k_max);
+/* The workgroups each select kernel of a call with these arguments is launched with now, on the current device:
+ * grids[0..3] = the level-0 count, the compaction, the last count, the append (one number, G: the kernels share
+ * their slices). G = min(CUs x resident workgroups per CU, 1024, max(64, tiles of 4096 keys in n)), capped by the
+ * hook below; a workgroup with more than one tile walks them in turn, one beyond the list has an empty slice.
+ * All 0 for k == 0. RSORT_ERR_NODEV without a device (the occupancy is the device's). */
+RSORT_API int    rsort_topk_grids(int64_t n, int64_t k, int pairs, int *grids);
+/* TEST HOOK (never set in production): workgroups > 0 caps G; 0 (the default) is no limit. Process-wide; returns the
+ * previous setting, or -RSORT_ERR_ARG for a negative value (nothing changes). */
+RSORT_API int    rsort_set_topk_grid_limit(int workgroups);
 
 /* ---------------------------------------------------------------- one digit pass, device */
 /* digit(key) = (key >> shift) & (bins - 1). Table layout: d_table[digit * num_chunks + chunk]. */
