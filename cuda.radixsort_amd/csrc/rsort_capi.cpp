@@ -1215,6 +1215,183 @@ int topk_host(const uint32_t *kin, const uint32_t *vin, int64_t n, int64_t k, in
     return hip_status(hipStreamSynchronize(s));
 }
 
+// ------------------------------------------------------------------------------ row-wise top-k
+// (rsort_topk_rows.hip.) Workspace of rsort_u32_topk_rows_device: the state words, the finishing sort's offsets
+// (i * k) and the segmented sort's own workspace for rows segments of k entries. As for the top-k, the regions
+// start at the caller's pointer rounded up to 256 (the slack in the formula).
+struct TopkRowsCarve {
+    uint32_t *state, *off;
+    void *seg_ws;
+    size_t seg_bytes, bytes;
+};
+
+TopkRowsCarve topk_rows_carve(int64_t rows, int64_t k, int pairs, void *ws) {
+    TopkRowsCarve c{};
+    char *q = (char *)(((uintptr_t)ws + 255u) & ~(uintptr_t)255u);
+    size_t o = 0;
+    c.state = (uint32_t *)(q + o);
+    o += 256;
+    c.off = (uint32_t *)(q + o);
+    o += align256((size_t)(rows + 1) * 4);
+    c.seg_ws = q + o;
+    c.seg_bytes = seg_carve(rows * k, rows, pairs, nullptr).bytes;
+    c.bytes = o + c.seg_bytes + 256;
+    return c;
+}
+
+std::atomic<int> g_topk_rows_grid_limit{0};  // rsort_set_topk_rows_grid_limit (tests); 0: no limit
+
+bool topk_rows_sizes_ok(int64_t rows, int64_t cols, int64_t k, int *st) {
+    *st = RSORT_OK;
+    if (rows < 0 || rows >= ((int64_t)1 << 31) || cols < 0 || cols >= ((int64_t)1 << 32)) *st = RSORT_ERR_SIZE;
+    else if (rows * cols >= ((int64_t)1 << 32)) *st = RSORT_ERR_SIZE;  // (< 2^63: both factors are in range)
+    else if (k < 0 || k > cols) *st = RSORT_ERR_ARG;
+    return *st == RSORT_OK;
+}
+
+// The select kernel's workgroups (the launch and rsort_topk_rows_grids share it): one per row (per four rows in
+// the wave class), at most four resident waves of workgroups, capped by the test hook; each strides over the rows.
+uint32_t topk_rows_grid(int64_t rows, int cls) {
+    const int64_t cus = std::max(1, device_cus());
+    const int64_t bpc = std::max(1, topk_rows_blocks_per_cu(cls));
+    int64_t g = std::min<int64_t>(cls == kTrWave ? (rows + 3) / 4 : rows, cus * bpc * 4);
+    const int limit = g_topk_rows_grid_limit.load();
+    if (limit > 0) g = std::min<int64_t>(g, limit);
+    return (uint32_t)g;
+}
+
+// The argument checks the device and the host entry share; *noop: nothing to do.
+int topk_rows_check_args(const void *kin, const void *vin, int64_t rows, int64_t cols, int64_t k, int flags,
+                         const void *kout, const void *vout, bool *noop) {
+    int st;
+    *noop = false;
+    if (!topk_rows_sizes_ok(rows, cols, k, &st)) return st;
+    if (flags & ~kTopkFlags) return RSORT_ERR_ARG;
+    if (flags & RSORT_TOPK_INDICES) {
+        if (vin != nullptr) return RSORT_ERR_ARG;
+    } else if ((vin != nullptr) != (vout != nullptr)) {
+        return RSORT_ERR_ARG;
+    }
+    if (rows == 0 || cols == 0 || k == 0) {
+        *noop = true;
+        return RSORT_OK;
+    }
+    if ((flags & RSORT_TOPK_INDICES) && vout == nullptr) return RSORT_ERR_ARG;
+    if (!kin || !kout) return RSORT_ERR_ARG;
+    return RSORT_OK;
+}
+
+int topk_rows_device(const uint32_t *kin, const uint32_t *vin, int64_t rows, int64_t cols, int64_t k, int flags,
+                     uint32_t *kout, uint32_t *vout, void *ws, size_t ws_bytes, hipStream_t s) {
+    bool noop;
+    int st = topk_rows_check_args(kin, vin, rows, cols, k, flags, kout, vout, &noop);
+    if (st || noop) return st;
+    if (!ws) return RSORT_ERR_ARG;
+    if (!aligned4(kin) || !aligned4(vin) || !aligned4(kout) || !aligned4(vout) || !aligned4(ws)) return RSORT_ERR_ALIGN;
+    const int pairs = vout != nullptr;
+    const TopkRowsCarve c = topk_rows_carve(rows, k, pairs, ws);
+    if (ws_bytes < c.bytes) return RSORT_ERR_WORKSPACE;
+
+    const int cls = topk_rows_class(cols);
+    const bool sorted = !(flags & RSORT_TOPK_UNSORTED);
+    const uint32_t m = (flags & RSORT_TOPK_LARGEST) ? 0xFFFFFFFFu : 0u;
+    if (hipMemsetAsync(c.state, 0, 256, s) != hipSuccess) return RSORT_ERR_HIP;
+    {
+        PhaseScope ps(RSORT_PHASE_SCATTER, rows * cols, s);
+        TopkRowsArgs a{};
+        a.kin = kin;
+        a.vin = vin;
+        a.kout = kout;
+        a.vout = vout;
+        a.state = c.state;
+        a.rows = (uint32_t)rows;
+        a.cols = (uint32_t)cols;
+        a.k = (uint32_t)k;
+        a.m = m;
+        a.pairs = !pairs ? kTrKeys : (flags & RSORT_TOPK_INDICES) ? kTrIndices : kTrValues;
+        a.raw = sorted ? 0u : 1u;
+        if ((st = hip_status(launch_topk_rows_select(cls, a, topk_rows_grid(rows, cls), s))))
+            return st;
+    }
+    if (!sorted) return RSORT_OK;
+    // the rows x k output holds x = key ^ m, every row's survivors in column order: the stable segmented sort of
+    // its rows, in place, is the contract's order
+    {
+        PhaseScope ps(RSORT_PHASE_COPY, rows + 1, s);
+        if ((st = hip_status(launch_topk_rows_offsets(c.off, (uint32_t)rows, (uint32_t)k, s)))) return st;
+    }
+    if ((st = seg_sort(kout, vout, kout, vout, rows * k, c.off, rows, c.seg_ws, c.seg_bytes, s))) return st;
+    if (m == 0) return RSORT_OK;
+    TopkCopyArgs cp{};
+    cp.kin = kout;  // the sorted x back to keys, in place
+    cp.kout = kout;
+    cp.n = cp.k = (uint64_t)(rows * k);
+    cp.m = m;
+    PhaseScope ps(RSORT_PHASE_COPY, rows * k, s);
+    return hip_status(launch_topk_copy(cp, s));
+}
+
+size_t topk_rows_workspace_size(int64_t rows, int64_t cols, int64_t k, int pairs) {
+    int st;
+    if (!topk_rows_sizes_ok(rows, cols, k, &st)) return 0;
+    return topk_rows_carve(rows, k, pairs, nullptr).bytes;
+}
+
+// {flags, report4} of the call that last ran in ws
+int topk_rows_read_check(int64_t rows, int64_t k, int pairs, void *ws, int *flags, int64_t *report4, hipStream_t s) {
+    const TopkRowsCarve c = topk_rows_carve(rows, k, pairs, ws);
+    uint32_t h[kTrSorted + 1] = {0}, check = 0;
+    int st;
+    if ((st = read_words(h, c.state, kTrSorted + 1, s))) return st;
+    if (h[kTrSorted]) {
+        const SegCarve sc = seg_carve(rows * k, rows, pairs, c.seg_ws);
+        if ((st = read_words(&check, sc.counters + kSegCheckWord, 1, s))) return st;
+    }
+    *flags = (int)(check & kCheckRankOrder);
+    if (report4) {
+        report4[0] = (int64_t)h[kTrClass];
+        report4[1] = (int64_t)h[kTrBadRows];
+    }
+    return RSORT_OK;
+}
+
+int topk_rows_host(const uint32_t *kin, const uint32_t *vin, int64_t rows, int64_t cols, int64_t k, int flags,
+                   uint32_t *kout, uint32_t *vout) {
+    bool noop;
+    int st = topk_rows_check_args(kin, vin, rows, cols, k, flags, kout, vout, &noop);
+    if (st || noop) return st;
+    const int pairs = vout != nullptr;
+    int count = 0, dev = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return RSORT_ERR_NODEV;
+    if (hipGetDevice(&dev) != hipSuccess) return RSORT_ERR_HIP;
+    DevCache *dc = cache_for(dev);
+    std::lock_guard<std::mutex> g(dc->mu);
+    const size_t n = (size_t)(rows * cols), nk = (size_t)(rows * k);
+    const size_t nb = align256(n * 4), kb = align256(nk * 4);
+    const size_t wsb = topk_rows_workspace_size(rows, cols, k, pairs);
+    if ((st = dc->reserve(2 * nb + 2 * kb + wsb))) return st;
+    char *q = (char *)dc->buf;
+    uint32_t *d_kin = (uint32_t *)q;
+    uint32_t *d_vin = vin ? (uint32_t *)(q + nb) : nullptr;
+    uint32_t *d_kout = (uint32_t *)(q + 2 * nb);
+    uint32_t *d_vout = pairs ? (uint32_t *)(q + 2 * nb + kb) : nullptr;
+    void *ws = q + 2 * nb + 2 * kb;
+    hipStream_t s = dc->stream;
+    if (hipMemcpyAsync(d_kin, kin, n * 4, hipMemcpyHostToDevice, s) != hipSuccess) return RSORT_ERR_HIP;
+    if (vin && hipMemcpyAsync(d_vin, vin, n * 4, hipMemcpyHostToDevice, s) != hipSuccess) return RSORT_ERR_HIP;
+    st = topk_rows_device(d_kin, d_vin, rows, cols, k, flags, d_kout, d_vout, ws, wsb, s);
+    if (st) {
+        (void)hipStreamSynchronize(s);
+        return st;
+    }
+    if (hipMemcpyAsync(kout, d_kout, nk * 4, hipMemcpyDeviceToHost, s) != hipSuccess) return RSORT_ERR_HIP;
+    if (pairs && hipMemcpyAsync(vout, d_vout, nk * 4, hipMemcpyDeviceToHost, s) != hipSuccess) return RSORT_ERR_HIP;
+    int check = 0;
+    int64_t rep[4] = {0, 0, 0, 0};
+    if ((st = topk_rows_read_check(rows, k, pairs, ws, &check, rep, s))) return st;
+    return (check || rep[1]) ? RSORT_ERR_CHECK : RSORT_OK;
+}
+
 }  // namespace
 
 void rsort::profile_pause(int delta) { t_prof_paused += delta; }
@@ -1433,6 +1610,55 @@ int rsort_topk_grids(int64_t n, int64_t k, int pairs, int *grids) {
 int rsort_set_topk_grid_limit(int workgroups) {
     if (workgroups < 0) return -RSORT_ERR_ARG;
     return g_topk_grid_limit.exchange(workgroups);
+}
+
+size_t rsort_topk_rows_workspace_size(int64_t rows, int64_t cols, int64_t k, int pairs) {
+    return topk_rows_workspace_size(rows, cols, k, pairs ? 1 : 0);
+}
+
+int rsort_u32_topk_rows_device(const uint32_t *d_keys_in, const uint32_t *d_vals_in, int64_t rows, int64_t cols,
+                               int64_t k, int flags, uint32_t *d_keys_out, uint32_t *d_vals_out, void *d_workspace,
+                               size_t workspace_bytes, void *stream) {
+    return topk_rows_device(d_keys_in, d_vals_in, rows, cols, k, flags, d_keys_out, d_vals_out, d_workspace,
+                            workspace_bytes, (hipStream_t)stream);
+}
+
+int rsort_u32_topk_rows(const uint32_t *keys, const uint32_t *vals, int64_t rows, int64_t cols, int64_t k, int flags,
+                        uint32_t *keys_out, uint32_t *vals_out) {
+    return topk_rows_host(keys, vals, rows, cols, k, flags, keys_out, vals_out);
+}
+
+int rsort_topk_rows_check(int64_t rows, int64_t cols, int64_t k, int pairs, const void *d_workspace, int *flags,
+                          int64_t *report4, void *stream) {
+    int st;
+    if (!flags) return RSORT_ERR_ARG;
+    *flags = 0;
+    if (report4) memset(report4, 0, 4 * sizeof(int64_t));
+    if (!topk_rows_sizes_ok(rows, cols, k, &st)) return st;
+    if (rows == 0 || cols == 0 || k == 0) return RSORT_OK;
+    if (!d_workspace) return RSORT_ERR_ARG;
+    return topk_rows_read_check(rows, k, pairs ? 1 : 0, const_cast<void *>(d_workspace), flags, report4,
+                                (hipStream_t)stream);
+}
+
+int rsort_topk_rows_grids(int64_t rows, int64_t cols, int64_t k, int pairs, int *grids2) {
+    int st;
+    (void)pairs;  // (keys and pairs run the same kernels)
+    if (!grids2) return RSORT_ERR_ARG;
+    grids2[0] = grids2[1] = 0;
+    if (!topk_rows_sizes_ok(rows, cols, k, &st)) return st;
+    if (rows == 0 || cols == 0 || k == 0) return RSORT_OK;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return RSORT_ERR_NODEV;
+    const int cls = topk_rows_class(cols);
+    grids2[0] = (int)topk_rows_grid(rows, cls);
+    grids2[1] = cls;
+    return RSORT_OK;
+}
+
+int rsort_set_topk_rows_grid_limit(int workgroups) {
+    if (workgroups < 0) return -RSORT_ERR_ARG;
+    return g_topk_rows_grid_limit.exchange(workgroups);
 }
 
 int rsort_pass_histogram(const rsort_plan *plan, const uint32_t *d_keys, int shift,

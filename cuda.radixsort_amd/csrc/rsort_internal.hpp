@@ -444,6 +444,33 @@ hipError_t launch_topk_copy(const TopkCopyArgs &a, hipStream_t s);
 // Fewest resident workgroups per CU over the select kernels (occupancy query), 0 on error.
 int topk_blocks_per_cu();
 
+// ------------------------------------------------------------------------------ row-wise top-k
+// (rsort_topk_rows.hip; rsort_u32_topk_rows_device.) One radix select per row of a rows x cols matrix, four 8-bit
+// levels from the top. cols is the call's, so the host picks the kernel: the segmented sort's limits and shapes.
+enum TopkRowsClass : int { kTrWave = 0, kTrSmall = 1, kTrLds = 2, kTrStream = 3 };
+inline int topk_rows_class(int64_t cols) {
+    return cols <= kSegWaveKeys ? kTrWave : cols <= kSegSmallKeys ? kTrSmall : cols <= kSegLdsKeys ? kTrLds : kTrStream;
+}
+// TopkRowsArgs::pairs
+enum TopkRowsPairs : uint32_t { kTrKeys = 0, kTrValues = 1, kTrIndices = 2 };
+// The call's 256 B of state, first in the workspace and cleared by the call's one memset: words 0..3 are what
+// rsort_topk_rows_check reports; kTrSorted: a finishing sort follows (its check word is then valid).
+enum TopkRowsWord : uint32_t { kTrClass = 0, kTrBadRows = 1, kTrSorted = 8 };
+struct TopkRowsArgs {
+    const uint32_t *kin, *vin;   // rows x cols (vin: kTrValues only)
+    uint32_t *kout, *vout;       // rows x k
+    uint32_t *state;
+    uint32_t rows, cols, k, m;
+    uint32_t pairs;              // TopkRowsPairs
+    uint32_t raw;                // 1 (UNSORTED): the outputs are keys; 0: x = key ^ m, for the finishing sort
+};
+// cls: TopkRowsClass; grid workgroups, each striding over the rows
+hipError_t launch_topk_rows_select(int cls, const TopkRowsArgs &a, uint32_t grid, hipStream_t s);
+// off[i] = i * k for i <= rows
+hipError_t launch_topk_rows_offsets(uint32_t *off, uint32_t rows, uint32_t k, hipStream_t s);
+// Resident workgroups per CU of a class's select kernel (occupancy query), 0 on error.
+int topk_rows_blocks_per_cu(int cls);
+
 // Raw next-digit tables (every workgroup of a pass sums the whole R x C table for its own starts) cost
 // O(R x C) reads per workgroup, O(R x C^2) per pass: only plans of at most this many chunks (about one
 // resident wave: C2 has 1024) take them; larger ones keep the tail scan (DESIGN §8 measured

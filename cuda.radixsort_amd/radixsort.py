@@ -249,6 +249,12 @@ SIGNATURES = {
     "rsort_topk_auto_limit": ([_i64, _int, ctypes.POINTER(_i64)], _int),
     "rsort_topk_grids": ([_i64, _i64, _int, ctypes.POINTER(_int)], _int),
     "rsort_set_topk_grid_limit": ([_int], _int),
+    "rsort_topk_rows_workspace_size": ([_i64, _i64, _i64, _int], _sz),
+    "rsort_u32_topk_rows_device": ([_vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _sz, _vp], _int),
+    "rsort_u32_topk_rows": ([_vp, _vp, _i64, _i64, _i64, _int, _vp, _vp], _int),
+    "rsort_topk_rows_check": ([_i64, _i64, _i64, _int, _vp, ctypes.POINTER(_int), ctypes.POINTER(_i64), _vp], _int),
+    "rsort_topk_rows_grids": ([_i64, _i64, _i64, _int, ctypes.POINTER(_int)], _int),
+    "rsort_set_topk_rows_grid_limit": ([_int], _int),
     "rsort_vendor_segmented_workspace_size": ([_i64, _i64], _sz),
     "rsort_u32_vendor_segmented_device": ([_vp, _vp, _i64, _vp, _i64, _vp, _sz, _vp], _int),
     "rsort_fingerprint_device": ([_vp, _vp, _i64, _vp, _vp], _int),
@@ -1181,6 +1187,111 @@ def topkByDevice(keys, k, largest=False, vals=None, indices=False, sorted=True):
     _check(_lib().rsort_u32_topk(keys.ctypes.data, vals.ctypes.data if vals is not None else None, n, k,
                                  _topk_flags(largest, indices, sorted), kout.ctypes.data,
                                  vout.ctypes.data if pairs else None), "topkByDevice")
+    return kout, vout
+
+
+# ---------------------------------------------------------------- row-wise top-k
+TOPK_ROWS_KERNELS = ("wave", "small", "lds", "stream")  # the kernel classes, by row length (include/rsort.h)
+
+
+def topk_rows_workspace_size(rows: int, cols: int, k: int, pairs: bool = False) -> int:
+    return int(_lib().rsort_topk_rows_workspace_size(int(rows), int(cols), int(k), 1 if pairs else 0))
+
+
+def topk_rows_grids(rows: int, cols: int, k: int, pairs: bool = False) -> dict:
+    """rsort_topk_rows_grids: {"workgroups": the select kernel's grid now, "kernel": its class, 0..3}."""
+    g = (ctypes.c_int * 2)()
+    _check(_lib().rsort_topk_rows_grids(int(rows), int(cols), int(k), 1 if pairs else 0, g), "rsort_topk_rows_grids")
+    return {"workgroups": int(g[0]), "kernel": int(g[1])}
+
+
+@contextmanager
+def topk_rows_grid_limit(workgroups: int):
+    """TEST HOOK (rsort_set_topk_rows_grid_limit): the row-wise select runs with at most `workgroups` workgroups,
+    so each strides over the rows; the previous setting comes back on exit."""
+    old = int(_lib().rsort_set_topk_rows_grid_limit(int(workgroups)))
+    if old < 0:
+        raise RSortError(-old, "rsort_set_topk_rows_grid_limit")
+    try:
+        yield
+    finally:
+        _lib().rsort_set_topk_rows_grid_limit(old)
+
+
+def _rows_2d(t, name, shape=None):
+    _need_torch()
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+        raise TypeError(f"{name} must be a torch int32 tensor (bits = u32)")
+    if t.dim() != 2 or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous 2-D tensor")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    return t
+
+
+def topk_rows(keys_2d, k, largest=False, vals_2d=None, indices=False, sorted=True, out=None, ws=None, stream=None):
+    """rsort_u32_topk_rows_device: the k smallest (largest=True: largest) keys of every row of a contiguous 2-D
+    torch int32 tensor (bits = u32 keys), with their values (vals_2d, same shape) or columns (indices=True);
+    stream-ordered. out: (keys_out, vals_out or None), rows x k each. Returns (keys_out[rows, k], vals_out or None,
+    workspace) -- what topk_rows_check needs."""
+    keys_2d = _rows_2d(keys_2d, "keys_2d")
+    rows, cols = keys_2d.shape
+    k = int(k)
+    if vals_2d is not None:
+        if indices:
+            raise ValueError("vals_2d and indices=True exclude each other")
+        vals_2d = _rows_2d(vals_2d, "vals_2d", (rows, cols))
+    pairs = vals_2d is not None or indices
+    if out is None:
+        kk = min(max(k, 0), cols)
+        out = (torch.empty((rows, kk), dtype=torch.int32, device=keys_2d.device),
+               torch.empty((rows, kk), dtype=torch.int32, device=keys_2d.device) if pairs else None)
+    else:
+        _rows_2d(out[0], "keys_out", (rows, k))
+        if pairs:
+            _rows_2d(out[1], "vals_out", (rows, k))
+        elif out[1] is not None:
+            raise ValueError("vals_out without vals_2d or indices=True")
+    kout, vout = out
+    if ws is None:
+        ws = workspace(topk_rows_workspace_size(rows, cols, k, pairs), keys_2d.device)
+    _check(_lib().rsort_u32_topk_rows_device(_ptr(keys_2d), _ptr(vals_2d), rows, cols, k,
+                                             _topk_flags(largest, indices, sorted), _ptr(kout), _ptr(vout), _ptr(ws),
+                                             ws.numel(), _stream(stream)), "rsort_u32_topk_rows_device")
+    return kout, vout, ws
+
+
+def topk_rows_check(rows: int, cols: int, k: int, pairs: bool, ws, stream=None) -> tuple[int, list]:
+    """rsort_topk_rows_check of the last row-wise call in `ws` (synchronises the stream): (flags, 0 = clean,
+    [kernel class, rows whose select did not write k entries, 0, 0])."""
+    f = ctypes.c_int()
+    r = (ctypes.c_int64 * 4)()
+    _check(_lib().rsort_topk_rows_check(int(rows), int(cols), int(k), 1 if pairs else 0, _ptr(ws), ctypes.byref(f), r,
+                                        _stream(stream)), "rsort_topk_rows_check")
+    return int(f.value), [int(v) for v in r]
+
+
+def topkRowsByDevice(keys_2d, k, largest=False, vals_2d=None, indices=False, sorted=True):
+    """rsort_u32_topk_rows over numpy host arrays (2-D, C-contiguous uint32): (keys_out, vals_out or None), rows x k
+    each. Synchronous."""
+    keys_2d = _host_u32(keys_2d, None, "keys_2d")
+    if keys_2d.ndim != 2:
+        raise ValueError("keys_2d must be 2-D")
+    rows, cols = keys_2d.shape
+    k = int(k)
+    if vals_2d is not None:
+        if indices:
+            raise ValueError("vals_2d and indices=True exclude each other")
+        vals_2d = _host_u32(vals_2d, None, "vals_2d")
+        if vals_2d.shape != keys_2d.shape:
+            raise ValueError("vals_2d must have the shape of keys_2d")
+    pairs = vals_2d is not None or indices
+    kk = min(max(k, 0), cols)
+    kout = np.empty((rows, kk), np.uint32)
+    vout = np.empty((rows, kk), np.uint32) if pairs else None
+    _check(_lib().rsort_u32_topk_rows(keys_2d.ctypes.data, vals_2d.ctypes.data if vals_2d is not None else None,
+                                      rows, cols, k, _topk_flags(largest, indices, sorted), kout.ctypes.data,
+                                      vout.ctypes.data if pairs else None), "topkRowsByDevice")
     return kout, vout
 
 

@@ -20,6 +20,7 @@
  *   (no counterpart)     rsort_u32_pairs*: key + u32 payload (BASELINE config 4)
  *   (no counterpart)     rsort_u32_segmented*: many independent segments of one array in one call
  *   (no counterpart)     rsort_u32_topk*: the k smallest or largest keys and their input positions
+ *   (no counterpart)     rsort_u32_topk_rows*: the same for every row of a matrix in one call
  *   (no counterpart)     rsort_partition_device / rsort_bucket_starts: the multi-GPU
  *                        key-range partition step (BASELINE config 5)
  *
@@ -308,6 +309,80 @@ RSORT_API int    rsort_topk_grids(int64_t n, int64_t k, int pairs, int *grids);
 /* TEST HOOK (never set in production): workgroups > 0 caps G; 0 (the default) is no limit. Process-wide; returns the
  * previous setting, or -RSORT_ERR_ARG for a negative value (nothing changes). */
 RSORT_API int    rsort_set_topk_grid_limit(int workgroups);
+
+/* ---------------------------------------------------------------- row-wise top-k */
+/* The k smallest or largest keys of EVERY ROW of a rows x cols matrix in one call (no reference counterpart; what a
+ * caller otherwise does with the segmented sort of all rows x cols keys and a slice, or with one rsort_u32_topk_device
+ * call -- eleven launches, a memset and a finishing sort -- per row).
+ *   - Input: `rows` contiguous rows of `cols` keys, row r = [r * cols, (r + 1) * cols). Output: rows x k, contiguous.
+ *   - `flags`: RSORT_TOPK_LARGEST | RSORT_TOPK_UNSORTED | RSORT_TOPK_INDICES, with the meaning they have in
+ *     rsort_u32_topk_device, applied to each row on its own. Let m = 0xFFFFFFFF with LARGEST, else 0: row r of the
+ *     output is the first k entries of the STABLE ascending sort of row r by key ^ m. Among the keys equal to a row's
+ *     k-th key those at the lowest columns are taken, and they stay in column order. With values the payload travels
+ *     with its key; with INDICES d_vals_in must be NULL and d_vals_out receives the COLUMN of each key, 0 .. cols - 1.
+ *     With UNSORTED each row returns the same k entries in an unspecified order. `pairs` in the size, check and grid
+ *     functions means "values or INDICES".
+ *   - Limits: 0 <= rows < 2^31, 0 <= cols, rows * cols < 2^32, 0 <= k <= cols; rows == 0, cols == 0 or k == 0 is a
+ *     no-op that needs no buffers.
+ *   - Buffers: any 4-byte alignment (keys, values, outputs, workspace). The outputs must not overlap the inputs; the
+ *     inputs are never written. The workspace's content on entry is arbitrary. Stream-ordered on `stream`, no
+ *     allocation, no host synchronisation, graph-capturable; the current device.
+ *   - Kernels: cols is the call's, so the class is picked on the host (rsort_topk_rows_grids reports it):
+ *       0 wave    1 .. 256 columns      one wave per row, four rows per 256-thread workgroup, no workgroup barrier
+ *       1 small   257 .. 1024           one 256-thread workgroup per row, 4 keys per lane
+ *       2 lds     1025 .. 16384         one 1024-thread workgroup per row, 16 keys per lane
+ *       3 stream  more                  one 1024-thread workgroup walks the row from global memory
+ *     Classes 0-2 read a row once, keep it in registers and run a radix select of the row's k-th key ^ m (up to four
+ *     8-bit levels over 256 LDS counters, per workgroup or, in the wave class, per wave; a level whose digit holds
+ *     exactly what is wanted is the last), then write the entries below it and the first of those equal to it, in
+ *     column order. Values are gathered for the selected entries only. The stream class reads its row once per level
+ *     and once more to write. It is the correctness net, not a fast path -- one CU selects from the whole row -- so
+ *     a caller with a handful of multi-million-key rows should loop rsort_u32_topk_device over them (8 x 2^23 keys,
+ *     k = 64: 16.8 ms here, 0.96 ms for that loop).
+ *   - Kernel resources (gfx950; VGPR / SGPR / LDS bytes; no scratch, no spills): wave 36 / 53 / 4096, small
+ *     37 / 65 / 1068, lds 95 / 65 / 1164 (1024 threads: within 128 VGPRs), stream 38 / 84 / 1164.
+ *   - Measured (MI355X, 2^26 uniform keys, keys only, sorted; DESIGN §5c, profiles/topk_rows.json), against the
+ *     segmented sort of all rows and a slice: 2^16 x 2^10, k = 16: 0.243 ms (0.385); 2^12 x 2^14, k = 16: 0.174 ms
+ *     (0.377), k = 1024: 0.241 (0.383); 2^8 x 2^18, k = 64: 0.541 (1.790). NOT faster: 2^20 x 64, k = 2 or 8:
+ *     1.54-1.61 ms (0.85), 0.8 of it the finishing sort of 2^20 k-key rows -- UNSORTED takes 0.28 ms there; and
+ *     k = cols / 2 at 2^12 x 2^14: 0.456 (0.423).
+ *   - Sorted output (no UNSORTED): the select leaves every row's k entries in column order and
+ *     rsort_u32_segmented_device's kernels sort the rows x k output in place (stable, so the result is the
+ *     contract's), after one small kernel that writes the offsets i * k; LARGEST adds one pass over the rows x k
+ *     keys. UNSORTED runs the select alone.
+ *   - Workspace bytes, with r(x) = x rounded up to a multiple of 256:
+ *         256                                                      the state and check words
+ *       + r(4 (rows + 1))                                          the finishing sort's offsets
+ *       + rsort_segmented_workspace_size(rows * k, rows, pairs)    the finishing sort
+ *       + 256                                                      alignment slack
+ *   - Errors, returned before any HIP call, in this order: RSORT_ERR_SIZE (rows, cols or rows * cols out of range),
+ *     RSORT_ERR_ARG (k out of range, unknown flag bits, exactly one of the two value pointers, INDICES with a non-NULL
+ *     d_vals_in or a NULL d_vals_out, NULL keys / output / workspace with work to do), RSORT_ERR_ALIGN,
+ *     RSORT_ERR_WORKSPACE.
+ *   - rsort_profile_begin/end: the select is RSORT_PHASE_SCATTER, the offsets and the LARGEST pass RSORT_PHASE_COPY;
+ *     the finishing sort reports its own phases. */
+RSORT_API size_t rsort_topk_rows_workspace_size(int64_t rows, int64_t cols, int64_t k, int pairs);
+RSORT_API int    rsort_u32_topk_rows_device(const uint32_t *d_keys_in, const uint32_t *d_vals_in, int64_t rows,
+                                            int64_t cols, int64_t k, int flags, uint32_t *d_keys_out,
+                                            uint32_t *d_vals_out, void *d_workspace, size_t workspace_bytes,
+                                            void *stream);
+/* host -> host, synchronous, library-owned cached workspace (as rsort_u32). RSORT_ERR_NODEV without a device (there
+ * is no CPU fallback); RSORT_ERR_CHECK when the check below is not clean. */
+RSORT_API int    rsort_u32_topk_rows(const uint32_t *keys, const uint32_t *vals, int64_t rows, int64_t cols, int64_t k,
+                                     int flags, uint32_t *keys_out, uint32_t *vals_out);
+/* After the call has completed on `stream` in `d_workspace`: *flags = the finishing sort's check bits
+ * (RSORT_CHECK_RANK_ORDER; 0 after an UNSORTED call); report4 (may be NULL) = {the kernel class 0..3, the rows whose
+ * select wrote a number of entries other than k (must be 0), 0, 0}. All 0 for a no-op call. Synchronises the stream. */
+RSORT_API int    rsort_topk_rows_check(int64_t rows, int64_t cols, int64_t k, int pairs, const void *d_workspace,
+                                       int *flags, int64_t *report4, void *stream);
+/* grids2 = {the select kernel's workgroups, its class} for a call with these arguments now, on the current device:
+ * min(rows [a quarter of it, rounded up, in the wave class], CUs x resident workgroups per CU x 4), capped by the hook
+ * below; each workgroup (each wave in the wave class) strides over the rows. Both 0 for a no-op call;
+ * RSORT_ERR_NODEV without a device otherwise (the occupancy is the device's). */
+RSORT_API int    rsort_topk_rows_grids(int64_t rows, int64_t cols, int64_t k, int pairs, int *grids2);
+/* TEST HOOK (never set in production), as rsort_set_topk_grid_limit: workgroups > 0 caps the select kernel's grid; 0
+ * (the default) is no limit. Process-wide; returns the previous setting, or -RSORT_ERR_ARG for a negative value. */
+RSORT_API int    rsort_set_topk_rows_grid_limit(int workgroups);
 
 /* ---------------------------------------------------------------- one digit pass, device */
 /* digit(key) = (key >> shift) & (bins - 1). Table layout: d_table[digit * num_chunks + chunk]. */
