@@ -104,6 +104,30 @@ int read_words(uint32_t *host, const uint32_t *dev, size_t words, hipStream_t s)
 
 bool aligned4(const void *p) { return ((uintptr_t)p & 3u) == 0; }
 
+// a key count every entry takes: [0, 2^32)
+bool key_count_ok(int64_t n) { return n >= 0 && n < ((int64_t)1 << 32); }
+
+bool have_device() {
+    int count = 0;
+    return hipGetDeviceCount(&count) == hipSuccess && count > 0;
+}
+
+// The one bump allocator of the workspace layouts (carve, seg_carve, topk_carve, topk_rows_carve) and of the host
+// entries' staging buffer (Staging): regions in the order they are taken, each a multiple of 256 B long, `off` the
+// bytes taken so far. A null base is sizing: take returns nullptr and only `off` counts. round_base: the regions start
+// at the base's next multiple of 256 (a caller's workspace of any 4-byte alignment).
+struct Bump {
+    char *base;
+    size_t off = 0;
+    explicit Bump(void *p, bool round_base = false)
+        : base(round_base ? (char *)(((uintptr_t)p + 255u) & ~(uintptr_t)255u) : (char *)p) {}
+    uint32_t *take(size_t bytes) {
+        uint32_t *q = base ? (uint32_t *)(base + off) : nullptr;
+        off += align256(bytes);
+        return q;
+    }
+};
+
 // The whole-line scatter kernels can write these outputs: any 4-B-aligned kout (launch_scatter
 // counts positions from its 128-B-aligned base, i.e. every position moves up by the < 32 keys
 // between that base and kout -- so n plus that shift must still fit the kernels' 32-bit positions);
@@ -116,8 +140,8 @@ bool line_capable(const void *kout, const void *vout, int pairs, int64_t n) {
 
 // ------------------------------------------------------------------------------ planning
 int device_cus() {
-    int dev = 0, count = 0, c = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return 0;
+    int dev = 0, c = 0;
+    if (!have_device()) return 0;
     if (hipGetDevice(&dev) != hipSuccess) return 0;
     if (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
     return c;
@@ -195,37 +219,32 @@ struct Carve {
 
 Carve carve(const rsort_plan &p, void *ws, bool partition = false) {
     Carve c{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        uint32_t *q = ws ? (uint32_t *)((char *)ws + off) : nullptr;
-        off += align256(bytes);
-        return q;
-    };
+    Bump b(ws);
     const size_t keys = (size_t)p.n * 4, table = (size_t)p.table_entries * 4;
-    c.tmp_k = take(keys);
-    if (p.pairs) c.tmp_v = take(keys);
-    c.table = take(table);
-    c.bsums = take((size_t)p.scan_blocks * 4);
-    c.starts = take((size_t)(p.bins + 1) * 4);
-    c.done = take(256);
+    c.tmp_k = b.take(keys);
+    if (p.pairs) c.tmp_v = b.take(keys);
+    c.table = b.take(table);
+    c.bsums = b.take((size_t)p.scan_blocks * 4);
+    c.starts = b.take((size_t)(p.bins + 1) * 4);
+    c.done = b.take(256);
     if (joint_plan(p)) {
         uint32_t **const region[] = {&c.joint, &c.bounds, &c.plan, &c.pcounts, &c.rows};
         static_assert(sizeof(region) / sizeof(region[0]) == sizeof(kJointRegionBytes) / sizeof(kJointRegionBytes[0]), "");
-        for (size_t i = 0; i < sizeof(region) / sizeof(region[0]); ++i) *region[i] = take(kJointRegionBytes[i]);
+        for (size_t i = 0; i < sizeof(region) / sizeof(region[0]); ++i) *region[i] = b.take(kJointRegionBytes[i]);
         if (c.joint) c.rows_cnt = c.joint + kJointBins * kJointBins;
     }
     if (!partition && next_plan(p)) {
-        c.table2 = take(table);
-        c.table3 = take(table);
+        c.table2 = b.take(table);
+        c.table3 = b.take(table);
     }
-    c.bytes = off;
+    c.bytes = b.off;
     return c;
 }
 
 int plan_fill(int64_t n, int k, int pairs, int64_t tpc, rsort_plan *p, int partition = 0) {
     if (!p) return RSORT_ERR_ARG;
     if (k < kMinBits || k > kMaxBits) return RSORT_ERR_BITS;
-    if (n < 0 || n >= ((int64_t)1 << 32)) return RSORT_ERR_SIZE;
+    if (!key_count_ok(n)) return RSORT_ERR_SIZE;
     if (tpc < 0) return RSORT_ERR_ARG;
     memset(p, 0, sizeof(*p));
     const int rank = g_rank_algo.load();
@@ -394,7 +413,7 @@ int run_scatter(const rsort_plan &p, const ScatterArgs &a, int dmode, hipStream_
 int check_plan(const rsort_plan *p) {
     if (!p) return RSORT_ERR_ARG;
     if (p->k_bits < kMinBits || p->k_bits > kMaxBits) return RSORT_ERR_BITS;
-    if (p->n < 0 || p->n >= ((int64_t)1 << 32)) return RSORT_ERR_SIZE;
+    if (!key_count_ok(p->n)) return RSORT_ERR_SIZE;
     // the tile shape must be one a kernel of this digit width exists for (keys or pairs): a plan is the planner's,
     // or a hand-made one that could be, never a shape that would only fail at its first launch
     const int geom = geom_from_shape(p->threads, p->tile_keys, p->pairs);
@@ -741,6 +760,47 @@ DevCache *cache_for(int dev) {
     return c;
 }
 
+// What the host entries share: the current device's cache, locked for the helper's lifetime, its buffer handed out
+// in 256-B-aligned regions (what the alignment-dependent routes count on: 16-B aligned keys, values at a multiple
+// of 16 B from them) and the copies on the cache's stream. A null device region is an optional array its call does
+// without: it copies nothing.
+struct Staging {
+    std::unique_lock<std::mutex> lock;
+    DevCache *dc = nullptr;
+    hipStream_t s = nullptr;
+    Bump regions{nullptr};
+
+    int open() {
+        int dev = 0;
+        if (!have_device()) return RSORT_ERR_NODEV;
+        if (hipGetDevice(&dev) != hipSuccess) return RSORT_ERR_HIP;
+        dc = cache_for(dev);
+        lock = std::unique_lock<std::mutex>(dc->mu);
+        return RSORT_OK;
+    }
+    // the buffer of one call: at least `total` bytes, its regions taken from the start
+    int reserve(size_t total) {
+        const int st = dc->reserve(total);
+        if (st) return st;
+        regions = Bump(dc->buf);
+        s = dc->stream;
+        return RSORT_OK;
+    }
+    uint32_t *words(size_t n) { return regions.take(n * 4); }
+    // words [at, at + n) of a host array and its device region
+    int upload(uint32_t *dev, const uint32_t *host, size_t n, size_t at = 0) {
+        return dev ? hip_status(hipMemcpyAsync(dev + at, host + at, n * 4, hipMemcpyHostToDevice, s)) : RSORT_OK;
+    }
+    int download(uint32_t *host, const uint32_t *dev, size_t n, size_t at = 0) {
+        return dev ? hip_status(hipMemcpyAsync(host + at, dev + at, n * 4, hipMemcpyDeviceToHost, s)) : RSORT_OK;
+    }
+    // a call that failed after its first launch: the stream is idle before the buffer is anyone else's
+    int drain(int st) {
+        (void)hipStreamSynchronize(s);
+        return st;
+    }
+};
+
 int host_sort(const uint32_t *kin, const uint32_t *vin, uint32_t *kout, uint32_t *vout,
               int64_t n, int k, rsort_phase_times *times) {
     const int pairs = vin != nullptr;
@@ -752,41 +812,24 @@ int host_sort(const uint32_t *kin, const uint32_t *vin, uint32_t *kout, uint32_t
         return RSORT_OK;
     }
     if (!kin || !kout || (pairs && !vout)) return RSORT_ERR_ARG;
-    int count = 0, dev = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return RSORT_ERR_NODEV;
-    if (hipGetDevice(&dev) != hipSuccess) return RSORT_ERR_HIP;
-    DevCache *dc = cache_for(dev);
-    std::lock_guard<std::mutex> g(dc->mu);
-    const size_t nb = align256((size_t)n * 4);
-    if ((st = dc->reserve(nb * (pairs ? 4 : 2) + p.workspace_bytes))) return st;
-    char *q = (char *)dc->buf;
-    uint32_t *d_kin = (uint32_t *)q;
-    uint32_t *d_kout = (uint32_t *)(q + nb);
-    uint32_t *d_vin = pairs ? (uint32_t *)(q + 2 * nb) : nullptr;
-    uint32_t *d_vout = pairs ? (uint32_t *)(q + 3 * nb) : nullptr;
-    void *ws = q + nb * (pairs ? 4 : 2);
-    hipStream_t s = dc->stream;
-    if (hipMemcpyAsync(d_kin, kin, (size_t)n * 4, hipMemcpyHostToDevice, s) != hipSuccess)
-        return RSORT_ERR_HIP;
-    if (pairs && hipMemcpyAsync(d_vin, vin, (size_t)n * 4, hipMemcpyHostToDevice, s) != hipSuccess)
-        return RSORT_ERR_HIP;
+    Staging h;
+    const size_t nw = (size_t)n, nb = align256(nw * 4);
+    if ((st = h.open()) || (st = h.reserve(nb * (pairs ? 4 : 2) + p.workspace_bytes))) return st;
+    uint32_t *const d_kin = h.words(nw), *const d_vin = pairs ? h.words(nw) : nullptr;
+    uint32_t *const d_kout = h.words(nw), *const d_vout = pairs ? h.words(nw) : nullptr;
+    void *const ws = h.regions.take(p.workspace_bytes);
+    if ((st = h.upload(d_kin, kin, nw)) || (st = h.upload(d_vin, vin, nw))) return st;
     if (times) rsort_profile_begin();
-    st = sort_planned(p, d_kin, d_vin, d_kout, d_vout, ws, p.workspace_bytes, s);
+    st = sort_planned(p, d_kin, d_vin, d_kout, d_vout, ws, p.workspace_bytes, h.s);
     if (times) {
         const int st2 = rsort_profile_end(times);
         if (!st) st = st2;
     }
-    if (st) {
-        (void)hipStreamSynchronize(s);
-        return st;
-    }
-    if (hipMemcpyAsync(kout, d_kout, (size_t)n * 4, hipMemcpyDeviceToHost, s) != hipSuccess)
-        return RSORT_ERR_HIP;
-    if (pairs && hipMemcpyAsync(vout, d_vout, (size_t)n * 4, hipMemcpyDeviceToHost, s) != hipSuccess)
-        return RSORT_ERR_HIP;
+    if (st) return h.drain(st);
+    if ((st = h.download(kout, d_kout, nw)) || (st = h.download(vout, d_vout, nw))) return st;
     // this entry waits for the device anyway: the sort's self-checks (rsort_plan_check) are read here
     uint32_t check = 0;
-    if ((st = read_words(&check, carve(p, ws).done + kDoneErr, 1, s))) return st;
+    if ((st = read_words(&check, carve(p, ws).done + kDoneErr, 1, h.s))) return st;
     return check ? RSORT_ERR_CHECK : RSORT_OK;
 }
 
@@ -799,28 +842,19 @@ struct SegCarve {
 };
 
 SegCarve seg_carve(int64_t n, int64_t nseg, int pairs, void *ws) {
-    SegCarve c;
-    char *q = (char *)ws;
-    size_t o = 0;
-    c.ktmp = (uint32_t *)(q + o);
-    o += align256((size_t)n * 4);
-    c.vtmp = pairs ? (uint32_t *)(q + o) : nullptr;
-    if (pairs) o += align256((size_t)n * 4);
-    for (int i = 0; i < kSegKinds; ++i) {
-        c.lists[i] = (uint32_t *)(q + o);
-        o += align256((size_t)nseg * 4);
-    }
-    c.counters = (uint32_t *)(q + o);
-    o += 256;
-    c.bytes = o;
+    SegCarve c{};
+    Bump b(ws);
+    c.ktmp = b.take((size_t)n * 4);
+    if (pairs) c.vtmp = b.take((size_t)n * 4);
+    for (int i = 0; i < kSegKinds; ++i) c.lists[i] = b.take((size_t)nseg * 4);
+    c.counters = b.take(256);
+    c.bytes = b.off;
     return c;
 }
 
-bool seg_sizes_ok(int64_t n, int64_t nseg, int *st) {
-    *st = RSORT_OK;
-    if (n < 0 || n >= ((int64_t)1 << 32)) *st = RSORT_ERR_SIZE;
-    else if (nseg < 0 || nseg >= ((int64_t)1 << 31)) *st = RSORT_ERR_ARG;
-    return *st == RSORT_OK;
+int seg_sizes(int64_t n, int64_t nseg) {
+    if (!key_count_ok(n)) return RSORT_ERR_SIZE;
+    return (nseg < 0 || nseg >= ((int64_t)1 << 31)) ? RSORT_ERR_ARG : RSORT_OK;
 }
 
 int seg_rank() { return internal_rank(g_rank_algo.load()) == kRankAtomic ? kRankAtomic : kRankCount; }
@@ -849,8 +883,8 @@ void seg_grids(int64_t n, int64_t nseg, int pairs, int rank, uint32_t grids[kSeg
 
 int seg_sort(const uint32_t *kin, const uint32_t *vin, uint32_t *kout, uint32_t *vout, int64_t n,
              const uint32_t *off, int64_t nseg, void *ws, size_t ws_bytes, hipStream_t s) {
-    int st;
-    if (!seg_sizes_ok(n, nseg, &st)) return st;
+    int st = seg_sizes(n, nseg);
+    if (st) return st;
     if ((vin != nullptr) != (vout != nullptr)) return RSORT_ERR_ARG;
     if (n == 0 || nseg == 0) return RSORT_OK;
     if (!kin || !kout || !off || !ws) return RSORT_ERR_ARG;
@@ -898,48 +932,32 @@ int seg_sort(const uint32_t *kin, const uint32_t *vin, uint32_t *kout, uint32_t 
 
 int seg_host_sort(const uint32_t *kin, const uint32_t *vin, uint32_t *kout, uint32_t *vout, int64_t n,
                   const uint32_t *off, int64_t nseg) {
-    int st;
-    if (!seg_sizes_ok(n, nseg, &st)) return st;
+    int st = seg_sizes(n, nseg);
+    if (st) return st;
     if ((vin != nullptr) != (vout != nullptr)) return RSORT_ERR_ARG;
     if (n == 0 || nseg == 0) return RSORT_OK;
     if (!kin || !kout || !off) return RSORT_ERR_ARG;
     for (int64_t i = 0; i < nseg; ++i)
         if (off[i] > off[i + 1] || (int64_t)off[i + 1] > n) return RSORT_ERR_ARG;
     const int pairs = vin != nullptr;
-    int count = 0, dev = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return RSORT_ERR_NODEV;
-    if (hipGetDevice(&dev) != hipSuccess) return RSORT_ERR_HIP;
+    Staging h;
+    if ((st = h.open())) return st;
     // the segments are contiguous: together they cover [lo, lo + m), and only that range travels
     const size_t lo = off[0], m = (size_t)off[nseg] - off[0];
     if (m == 0) return RSORT_OK;
-    DevCache *dc = cache_for(dev);
-    std::lock_guard<std::mutex> g(dc->mu);
-    const size_t nb = align256((size_t)n * 4), ob = align256((size_t)(nseg + 1) * 4);
+    const size_t nw = (size_t)n, ow = (size_t)nseg + 1;
     const size_t wsb = seg_carve(n, nseg, pairs, nullptr).bytes;
-    if ((st = dc->reserve(nb * (pairs ? 4 : 2) + ob + wsb))) return st;
-    char *q = (char *)dc->buf;
-    uint32_t *d_kin = (uint32_t *)q;
-    uint32_t *d_kout = (uint32_t *)(q + nb);
-    uint32_t *d_vin = pairs ? (uint32_t *)(q + 2 * nb) : nullptr;
-    uint32_t *d_vout = pairs ? (uint32_t *)(q + 3 * nb) : nullptr;
-    uint32_t *d_off = (uint32_t *)(q + nb * (pairs ? 4 : 2));
-    void *ws = q + nb * (pairs ? 4 : 2) + ob;
-    hipStream_t s = dc->stream;
-    if (hipMemcpyAsync(d_kin + lo, kin + lo, m * 4, hipMemcpyHostToDevice, s) != hipSuccess) return RSORT_ERR_HIP;
-    if (pairs && hipMemcpyAsync(d_vin + lo, vin + lo, m * 4, hipMemcpyHostToDevice, s) != hipSuccess)
-        return RSORT_ERR_HIP;
-    if (hipMemcpyAsync(d_off, off, (size_t)(nseg + 1) * 4, hipMemcpyHostToDevice, s) != hipSuccess)
-        return RSORT_ERR_HIP;
-    st = seg_sort(d_kin, d_vin, d_kout, d_vout, n, d_off, nseg, ws, wsb, s);
-    if (st) {
-        (void)hipStreamSynchronize(s);
+    if ((st = h.reserve(align256(nw * 4) * (pairs ? 4 : 2) + align256(ow * 4) + wsb))) return st;
+    uint32_t *const d_kin = h.words(nw), *const d_vin = pairs ? h.words(nw) : nullptr;
+    uint32_t *const d_kout = h.words(nw), *const d_vout = pairs ? h.words(nw) : nullptr;
+    uint32_t *const d_off = h.words(ow);
+    void *const ws = h.regions.take(wsb);
+    if ((st = h.upload(d_kin, kin, m, lo)) || (st = h.upload(d_vin, vin, m, lo)) || (st = h.upload(d_off, off, ow)))
         return st;
-    }
-    if (hipMemcpyAsync(kout + lo, d_kout + lo, m * 4, hipMemcpyDeviceToHost, s) != hipSuccess) return RSORT_ERR_HIP;
-    if (pairs && hipMemcpyAsync(vout + lo, d_vout + lo, m * 4, hipMemcpyDeviceToHost, s) != hipSuccess)
-        return RSORT_ERR_HIP;
+    if ((st = seg_sort(d_kin, d_vin, d_kout, d_vout, n, d_off, nseg, ws, wsb, h.s))) return h.drain(st);
+    if ((st = h.download(kout, d_kout, m, lo)) || (st = h.download(vout, d_vout, m, lo))) return st;
     uint32_t check = 0;
-    if ((st = read_words(&check, seg_carve(n, nseg, pairs, ws).counters + kSegCheckWord, 1, s))) return st;
+    if ((st = read_words(&check, seg_carve(n, nseg, pairs, ws).counters + kSegCheckWord, 1, h.s))) return st;
     return check ? RSORT_ERR_CHECK : RSORT_OK;
 }
 
@@ -962,31 +980,25 @@ struct TopkCarve {
 // route: RSORT_TOPK_SELECT or RSORT_TOPK_SORT; plan: the finishing sort's (k entries) or the whole sort's (n)
 TopkCarve topk_carve(int64_t n, int64_t k, int pairs, int route, const rsort_plan &plan, void *ws) {
     TopkCarve c{};
-    char *q = (char *)(((uintptr_t)ws + 255u) & ~(uintptr_t)255u);
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        uint32_t *p = (uint32_t *)(q + o);
-        o += align256(bytes);
-        return p;
-    };
-    c.state = take(256);
+    Bump b(ws, /*round_base=*/true);
+    c.state = b.take(256);
     if (route == RSORT_TOPK_SELECT) {
-        c.totals = take((size_t)kTopkTotalsWords * 4);
-        c.rows_cnt = take((size_t)kTopkMaxGrid * kTopkBins0 * 4);
-        c.rows_pre = take((size_t)kTopkMaxGrid * kTopkBins0 * 4);
-        c.offs0 = take((size_t)kTopkMaxGrid * 8);
-        c.offs1 = take((size_t)kTopkMaxGrid * 8);
-        c.wk = take((size_t)k * 4);
-        c.wv = pairs ? take((size_t)k * 4) : nullptr;
-        c.ak = take((size_t)n * 4);
-        c.av = pairs ? take((size_t)n * 4) : nullptr;
+        c.totals = b.take((size_t)kTopkTotalsWords * 4);
+        c.rows_cnt = b.take((size_t)kTopkMaxGrid * kTopkBins0 * 4);
+        c.rows_pre = b.take((size_t)kTopkMaxGrid * kTopkBins0 * 4);
+        c.offs0 = b.take((size_t)kTopkMaxGrid * 8);
+        c.offs1 = b.take((size_t)kTopkMaxGrid * 8);
+        c.wk = b.take((size_t)k * 4);
+        if (pairs) c.wv = b.take((size_t)k * 4);
+        c.ak = b.take((size_t)n * 4);
+        if (pairs) c.av = b.take((size_t)n * 4);
     } else {
-        c.sk = take((size_t)n * 4);
-        c.sv = pairs ? take((size_t)n * 4) : nullptr;
+        c.sk = b.take((size_t)n * 4);
+        if (pairs) c.sv = b.take((size_t)n * 4);
     }
-    c.sort_ws = q + o;
-    c.sort_bytes = plan.workspace_bytes;
-    c.bytes = o + c.sort_bytes + 256;
+    c.sort_bytes = plan.workspace_bytes;  // (a sum of whole regions itself)
+    c.sort_ws = b.take(c.sort_bytes);
+    c.bytes = b.off + 256;
     return c;
 }
 
@@ -995,11 +1007,9 @@ std::atomic<int> g_topk_grid_limit{0};  // rsort_set_topk_grid_limit (tests); 0:
 
 constexpr int kTopkFlags = RSORT_TOPK_LARGEST | RSORT_TOPK_UNSORTED | RSORT_TOPK_INDICES;
 
-bool topk_sizes_ok(int64_t n, int64_t k, int *st) {
-    *st = RSORT_OK;
-    if (n < 0 || n >= ((int64_t)1 << 32)) *st = RSORT_ERR_SIZE;
-    else if (k < 0 || k > n) *st = RSORT_ERR_ARG;
-    return *st == RSORT_OK;
+int topk_sizes(int64_t n, int64_t k) {
+    if (!key_count_ok(n)) return RSORT_ERR_SIZE;
+    return (k < 0 || k > n) ? RSORT_ERR_ARG : RSORT_OK;
 }
 
 int64_t topk_auto_limit(int64_t n, int pairs) { return n / kTopkAutoDiv[pairs ? 1 : 0]; }
@@ -1027,19 +1037,19 @@ uint32_t topk_grid(int64_t n) {
     return (uint32_t)g;
 }
 
-// The argument checks the device and the host entry share; *noop: nothing to do (k == 0).
-int topk_check(const void *kin, const void *vin, int64_t n, int64_t k, int flags, const void *kout, const void *vout,
-               bool *noop) {
-    int st;
+// The argument checks the device and the host entries of the top-k and the row-wise top-k share. size_st: the
+// status of the call's own size test (topk_sizes, topk_rows_sizes); nothing: its sizes leave nothing to do (*noop).
+int topk_check(int size_st, bool nothing, const void *kin, const void *vin, int flags, const void *kout,
+               const void *vout, bool *noop) {
     *noop = false;
-    if (!topk_sizes_ok(n, k, &st)) return st;
+    if (size_st) return size_st;
     if (flags & ~kTopkFlags) return RSORT_ERR_ARG;
     if (flags & RSORT_TOPK_INDICES) {
         if (vin != nullptr) return RSORT_ERR_ARG;
     } else if ((vin != nullptr) != (vout != nullptr)) {
         return RSORT_ERR_ARG;
     }
-    if (k == 0) {
+    if (nothing) {
         *noop = true;
         return RSORT_OK;
     }
@@ -1158,7 +1168,7 @@ int topk_sort(const uint32_t *kin, const uint32_t *vin, int64_t n, int64_t k, in
 int topk_device(const uint32_t *kin, const uint32_t *vin, int64_t n, int64_t k, int flags, uint32_t *kout,
                 uint32_t *vout, void *ws, size_t ws_bytes, hipStream_t s) {
     bool noop;
-    int st = topk_check(kin, vin, n, k, flags, kout, vout, &noop);
+    int st = topk_check(topk_sizes(n, k), k == 0, kin, vin, flags, kout, vout, &noop);
     if (st || noop) return st;
     if (!ws) return RSORT_ERR_ARG;
     if (!aligned4(kin) || !aligned4(vin) || !aligned4(kout) || !aligned4(vout) || !aligned4(ws)) return RSORT_ERR_ALIGN;
@@ -1173,8 +1183,7 @@ int topk_device(const uint32_t *kin, const uint32_t *vin, int64_t n, int64_t k, 
 }
 
 size_t topk_workspace_size(int64_t n, int64_t k, int pairs, int route) {
-    int st;
-    if (!topk_sizes_ok(n, k, &st) || route < RSORT_TOPK_AUTO || route > RSORT_TOPK_SORT) return 0;
+    if (topk_sizes(n, k) || route < RSORT_TOPK_AUTO || route > RSORT_TOPK_SORT) return 0;
     route = topk_resolve(route, n, k, pairs);
     rsort_plan plan;
     if (topk_plan(n, k, pairs, route, &plan)) return 0;
@@ -1184,35 +1193,20 @@ size_t topk_workspace_size(int64_t n, int64_t k, int pairs, int route) {
 int topk_host(const uint32_t *kin, const uint32_t *vin, int64_t n, int64_t k, int flags, uint32_t *kout,
               uint32_t *vout) {
     bool noop;
-    int st = topk_check(kin, vin, n, k, flags, kout, vout, &noop);
+    int st = topk_check(topk_sizes(n, k), k == 0, kin, vin, flags, kout, vout, &noop);
     if (st || noop) return st;
-    const int pairs = vout != nullptr;
-    int count = 0, dev = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return RSORT_ERR_NODEV;
-    if (hipGetDevice(&dev) != hipSuccess) return RSORT_ERR_HIP;
-    DevCache *dc = cache_for(dev);
-    std::lock_guard<std::mutex> g(dc->mu);
-    const size_t nb = align256((size_t)n * 4), kb = align256((size_t)k * 4);
+    const int pairs = vout != nullptr;  // (values, or indices: then there is no vin)
+    Staging h;
+    const size_t nw = (size_t)n, kw = (size_t)k;
     const size_t wsb = topk_workspace_size(n, k, pairs, g_topk_route.load());
-    if ((st = dc->reserve(2 * nb + 2 * kb + wsb))) return st;
-    char *q = (char *)dc->buf;
-    uint32_t *d_kin = (uint32_t *)q;
-    uint32_t *d_vin = vin ? (uint32_t *)(q + nb) : nullptr;
-    uint32_t *d_kout = (uint32_t *)(q + 2 * nb);
-    uint32_t *d_vout = pairs ? (uint32_t *)(q + 2 * nb + kb) : nullptr;
-    void *ws = q + 2 * nb + 2 * kb;
-    hipStream_t s = dc->stream;
-    if (hipMemcpyAsync(d_kin, kin, (size_t)n * 4, hipMemcpyHostToDevice, s) != hipSuccess) return RSORT_ERR_HIP;
-    if (vin && hipMemcpyAsync(d_vin, vin, (size_t)n * 4, hipMemcpyHostToDevice, s) != hipSuccess) return RSORT_ERR_HIP;
-    st = topk_device(d_kin, d_vin, n, k, flags, d_kout, d_vout, ws, wsb, s);
-    if (st) {
-        (void)hipStreamSynchronize(s);
-        return st;
-    }
-    if (hipMemcpyAsync(kout, d_kout, (size_t)k * 4, hipMemcpyDeviceToHost, s) != hipSuccess) return RSORT_ERR_HIP;
-    if (pairs && hipMemcpyAsync(vout, d_vout, (size_t)k * 4, hipMemcpyDeviceToHost, s) != hipSuccess)
-        return RSORT_ERR_HIP;
-    return hip_status(hipStreamSynchronize(s));
+    if ((st = h.open()) || (st = h.reserve(2 * align256(nw * 4) + 2 * align256(kw * 4) + wsb))) return st;
+    uint32_t *const d_kin = h.words(nw), *const d_vin = vin ? h.words(nw) : nullptr;
+    uint32_t *const d_kout = h.words(kw), *const d_vout = pairs ? h.words(kw) : nullptr;
+    void *const ws = h.regions.take(wsb);
+    if ((st = h.upload(d_kin, kin, nw)) || (st = h.upload(d_vin, vin, nw))) return st;
+    if ((st = topk_device(d_kin, d_vin, n, k, flags, d_kout, d_vout, ws, wsb, h.s))) return h.drain(st);
+    if ((st = h.download(kout, d_kout, kw)) || (st = h.download(vout, d_vout, kw))) return st;
+    return hip_status(hipStreamSynchronize(h.s));
 }
 
 // ------------------------------------------------------------------------------ row-wise top-k
@@ -1227,26 +1221,21 @@ struct TopkRowsCarve {
 
 TopkRowsCarve topk_rows_carve(int64_t rows, int64_t k, int pairs, void *ws) {
     TopkRowsCarve c{};
-    char *q = (char *)(((uintptr_t)ws + 255u) & ~(uintptr_t)255u);
-    size_t o = 0;
-    c.state = (uint32_t *)(q + o);
-    o += 256;
-    c.off = (uint32_t *)(q + o);
-    o += align256((size_t)(rows + 1) * 4);
-    c.seg_ws = q + o;
+    Bump b(ws, /*round_base=*/true);
+    c.state = b.take(256);
+    c.off = b.take((size_t)(rows + 1) * 4);
     c.seg_bytes = seg_carve(rows * k, rows, pairs, nullptr).bytes;
-    c.bytes = o + c.seg_bytes + 256;
+    c.seg_ws = b.take(c.seg_bytes);
+    c.bytes = b.off + 256;
     return c;
 }
 
 std::atomic<int> g_topk_rows_grid_limit{0};  // rsort_set_topk_rows_grid_limit (tests); 0: no limit
 
-bool topk_rows_sizes_ok(int64_t rows, int64_t cols, int64_t k, int *st) {
-    *st = RSORT_OK;
-    if (rows < 0 || rows >= ((int64_t)1 << 31) || cols < 0 || cols >= ((int64_t)1 << 32)) *st = RSORT_ERR_SIZE;
-    else if (rows * cols >= ((int64_t)1 << 32)) *st = RSORT_ERR_SIZE;  // (< 2^63: both factors are in range)
-    else if (k < 0 || k > cols) *st = RSORT_ERR_ARG;
-    return *st == RSORT_OK;
+int topk_rows_sizes(int64_t rows, int64_t cols, int64_t k) {
+    if (rows < 0 || rows >= ((int64_t)1 << 31) || !key_count_ok(cols)) return RSORT_ERR_SIZE;
+    if (!key_count_ok(rows * cols)) return RSORT_ERR_SIZE;  // (< 2^63: both factors are in range)
+    return (k < 0 || k > cols) ? RSORT_ERR_ARG : RSORT_OK;
 }
 
 // The select kernel's workgroups (the launch and rsort_topk_rows_grids share it): one per row (per four rows in
@@ -1260,31 +1249,14 @@ uint32_t topk_rows_grid(int64_t rows, int cls) {
     return (uint32_t)g;
 }
 
-// The argument checks the device and the host entry share; *noop: nothing to do.
-int topk_rows_check_args(const void *kin, const void *vin, int64_t rows, int64_t cols, int64_t k, int flags,
-                         const void *kout, const void *vout, bool *noop) {
-    int st;
-    *noop = false;
-    if (!topk_rows_sizes_ok(rows, cols, k, &st)) return st;
-    if (flags & ~kTopkFlags) return RSORT_ERR_ARG;
-    if (flags & RSORT_TOPK_INDICES) {
-        if (vin != nullptr) return RSORT_ERR_ARG;
-    } else if ((vin != nullptr) != (vout != nullptr)) {
-        return RSORT_ERR_ARG;
-    }
-    if (rows == 0 || cols == 0 || k == 0) {
-        *noop = true;
-        return RSORT_OK;
-    }
-    if ((flags & RSORT_TOPK_INDICES) && vout == nullptr) return RSORT_ERR_ARG;
-    if (!kin || !kout) return RSORT_ERR_ARG;
-    return RSORT_OK;
-}
+// nothing to do: no rows, no columns or k = 0
+bool topk_rows_empty(int64_t rows, int64_t cols, int64_t k) { return rows == 0 || cols == 0 || k == 0; }
 
 int topk_rows_device(const uint32_t *kin, const uint32_t *vin, int64_t rows, int64_t cols, int64_t k, int flags,
                      uint32_t *kout, uint32_t *vout, void *ws, size_t ws_bytes, hipStream_t s) {
     bool noop;
-    int st = topk_rows_check_args(kin, vin, rows, cols, k, flags, kout, vout, &noop);
+    int st = topk_check(topk_rows_sizes(rows, cols, k), topk_rows_empty(rows, cols, k), kin, vin, flags, kout, vout,
+                        &noop);
     if (st || noop) return st;
     if (!ws) return RSORT_ERR_ARG;
     if (!aligned4(kin) || !aligned4(vin) || !aligned4(kout) || !aligned4(vout) || !aligned4(ws)) return RSORT_ERR_ALIGN;
@@ -1332,8 +1304,7 @@ int topk_rows_device(const uint32_t *kin, const uint32_t *vin, int64_t rows, int
 }
 
 size_t topk_rows_workspace_size(int64_t rows, int64_t cols, int64_t k, int pairs) {
-    int st;
-    if (!topk_rows_sizes_ok(rows, cols, k, &st)) return 0;
+    if (topk_rows_sizes(rows, cols, k)) return 0;
     return topk_rows_carve(rows, k, pairs, nullptr).bytes;
 }
 
@@ -1358,38 +1329,29 @@ int topk_rows_read_check(int64_t rows, int64_t k, int pairs, void *ws, int *flag
 int topk_rows_host(const uint32_t *kin, const uint32_t *vin, int64_t rows, int64_t cols, int64_t k, int flags,
                    uint32_t *kout, uint32_t *vout) {
     bool noop;
-    int st = topk_rows_check_args(kin, vin, rows, cols, k, flags, kout, vout, &noop);
+    int st = topk_check(topk_rows_sizes(rows, cols, k), topk_rows_empty(rows, cols, k), kin, vin, flags, kout, vout,
+                        &noop);
     if (st || noop) return st;
     const int pairs = vout != nullptr;
-    int count = 0, dev = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return RSORT_ERR_NODEV;
-    if (hipGetDevice(&dev) != hipSuccess) return RSORT_ERR_HIP;
-    DevCache *dc = cache_for(dev);
-    std::lock_guard<std::mutex> g(dc->mu);
-    const size_t n = (size_t)(rows * cols), nk = (size_t)(rows * k);
-    const size_t nb = align256(n * 4), kb = align256(nk * 4);
+    Staging h;
+    const size_t nw = (size_t)(rows * cols), kw = (size_t)(rows * k);
     const size_t wsb = topk_rows_workspace_size(rows, cols, k, pairs);
-    if ((st = dc->reserve(2 * nb + 2 * kb + wsb))) return st;
-    char *q = (char *)dc->buf;
-    uint32_t *d_kin = (uint32_t *)q;
-    uint32_t *d_vin = vin ? (uint32_t *)(q + nb) : nullptr;
-    uint32_t *d_kout = (uint32_t *)(q + 2 * nb);
-    uint32_t *d_vout = pairs ? (uint32_t *)(q + 2 * nb + kb) : nullptr;
-    void *ws = q + 2 * nb + 2 * kb;
-    hipStream_t s = dc->stream;
-    if (hipMemcpyAsync(d_kin, kin, n * 4, hipMemcpyHostToDevice, s) != hipSuccess) return RSORT_ERR_HIP;
-    if (vin && hipMemcpyAsync(d_vin, vin, n * 4, hipMemcpyHostToDevice, s) != hipSuccess) return RSORT_ERR_HIP;
-    st = topk_rows_device(d_kin, d_vin, rows, cols, k, flags, d_kout, d_vout, ws, wsb, s);
-    if (st) {
-        (void)hipStreamSynchronize(s);
-        return st;
-    }
-    if (hipMemcpyAsync(kout, d_kout, nk * 4, hipMemcpyDeviceToHost, s) != hipSuccess) return RSORT_ERR_HIP;
-    if (pairs && hipMemcpyAsync(vout, d_vout, nk * 4, hipMemcpyDeviceToHost, s) != hipSuccess) return RSORT_ERR_HIP;
+    if ((st = h.open()) || (st = h.reserve(2 * align256(nw * 4) + 2 * align256(kw * 4) + wsb))) return st;
+    uint32_t *const d_kin = h.words(nw), *const d_vin = vin ? h.words(nw) : nullptr;
+    uint32_t *const d_kout = h.words(kw), *const d_vout = pairs ? h.words(kw) : nullptr;
+    void *const ws = h.regions.take(wsb);
+    if ((st = h.upload(d_kin, kin, nw)) || (st = h.upload(d_vin, vin, nw))) return st;
+    if ((st = topk_rows_device(d_kin, d_vin, rows, cols, k, flags, d_kout, d_vout, ws, wsb, h.s))) return h.drain(st);
+    if ((st = h.download(kout, d_kout, kw)) || (st = h.download(vout, d_vout, kw))) return st;
     int check = 0;
     int64_t rep[4] = {0, 0, 0, 0};
-    if ((st = topk_rows_read_check(rows, k, pairs, ws, &check, rep, s))) return st;
+    if ((st = topk_rows_read_check(rows, k, pairs, ws, &check, rep, h.s))) return st;
     return (check || rep[1]) ? RSORT_ERR_CHECK : RSORT_OK;
+}
+
+// rsort_set_*_grid_limit (test hooks): the limit before, or -RSORT_ERR_ARG
+int set_grid_limit(std::atomic<int> &limit, int workgroups) {
+    return workgroups < 0 ? -RSORT_ERR_ARG : limit.exchange(workgroups);
 }
 
 }  // namespace
@@ -1487,8 +1449,7 @@ int rsort_segmented_capacity(int pairs, int *small_keys, int *lds_keys) {
 }
 
 size_t rsort_segmented_workspace_size(int64_t n, int64_t num_segments, int pairs) {
-    int st;
-    if (!seg_sizes_ok(n, num_segments, &st)) return 0;
+    if (seg_sizes(n, num_segments)) return 0;
     return seg_carve(n, num_segments, pairs ? 1 : 0, nullptr).bytes;
 }
 
@@ -1505,7 +1466,7 @@ int rsort_segmented_check(int64_t n, int64_t num_segments, int pairs, const void
     if (!flags) return RSORT_ERR_ARG;
     *flags = 0;
     if (class_counts) memset(class_counts, 0, 4 * sizeof(int64_t));
-    if (!seg_sizes_ok(n, num_segments, &st)) return st;
+    if ((st = seg_sizes(n, num_segments))) return st;
     if (n == 0 || num_segments == 0) return RSORT_OK;
     if (!d_workspace) return RSORT_ERR_ARG;
     const SegCarve c = seg_carve(n, num_segments, pairs ? 1 : 0, const_cast<void *>(d_workspace));
@@ -1525,20 +1486,16 @@ int rsort_segmented_grids(int64_t n, int64_t num_segments, int pairs, int *grids
     int st;
     if (!grids) return RSORT_ERR_ARG;
     for (int i = 0; i < kSegKinds; ++i) grids[i] = 0;
-    if (!seg_sizes_ok(n, num_segments, &st)) return st;
+    if ((st = seg_sizes(n, num_segments))) return st;
     if (n == 0 || num_segments == 0) return RSORT_OK;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return RSORT_ERR_NODEV;
+    if (!have_device()) return RSORT_ERR_NODEV;
     uint32_t g[kSegKinds];
     seg_grids(n, num_segments, pairs ? 1 : 0, seg_rank(), g);
     for (int i = 0; i < kSegKinds; ++i) grids[i] = (int)g[i];
     return RSORT_OK;
 }
 
-int rsort_set_segmented_grid_limit(int workgroups) {
-    if (workgroups < 0) return -RSORT_ERR_ARG;
-    return g_seg_grid_limit.exchange(workgroups);
-}
+int rsort_set_segmented_grid_limit(int workgroups) { return set_grid_limit(g_seg_grid_limit, workgroups); }
 
 int rsort_u32_segmented(const uint32_t *keys_in, const uint32_t *vals_in, uint32_t *keys_out, uint32_t *vals_out,
                         int64_t n, const uint32_t *offsets, int64_t num_segments) {
@@ -1566,7 +1523,7 @@ int rsort_topk_report(int64_t n, int64_t k, int pairs, const void *d_workspace, 
     (void)pairs;  // (the state words come first in the workspace whatever the layout behind them)
     if (!report8) return RSORT_ERR_ARG;
     for (int i = 0; i < 8; ++i) report8[i] = 0;
-    if (!topk_sizes_ok(n, k, &st)) return st;
+    if ((st = topk_sizes(n, k))) return st;
     if (k == 0) return RSORT_OK;
     if (!d_workspace) return RSORT_ERR_ARG;
     const rsort_plan none{};
@@ -1588,7 +1545,7 @@ int rsort_get_topk_route(void) { return g_topk_route.load(); }
 int rsort_topk_auto_limit(int64_t n, int pairs, int64_t *k_max) {
     if (!k_max) return RSORT_ERR_ARG;
     *k_max = 0;
-    if (n < 0 || n >= ((int64_t)1 << 32)) return RSORT_ERR_SIZE;
+    if (!key_count_ok(n)) return RSORT_ERR_SIZE;
     *k_max = topk_auto_limit(n, pairs ? 1 : 0);
     return RSORT_OK;
 }
@@ -1598,19 +1555,15 @@ int rsort_topk_grids(int64_t n, int64_t k, int pairs, int *grids) {
     (void)pairs;  // (keys and pairs run the same kernels)
     if (!grids) return RSORT_ERR_ARG;
     for (int i = 0; i < 4; ++i) grids[i] = 0;
-    if (!topk_sizes_ok(n, k, &st)) return st;
+    if ((st = topk_sizes(n, k))) return st;
     if (k == 0) return RSORT_OK;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return RSORT_ERR_NODEV;
+    if (!have_device()) return RSORT_ERR_NODEV;
     const int g = (int)topk_grid(n);
     for (int i = 0; i < 4; ++i) grids[i] = g;
     return RSORT_OK;
 }
 
-int rsort_set_topk_grid_limit(int workgroups) {
-    if (workgroups < 0) return -RSORT_ERR_ARG;
-    return g_topk_grid_limit.exchange(workgroups);
-}
+int rsort_set_topk_grid_limit(int workgroups) { return set_grid_limit(g_topk_grid_limit, workgroups); }
 
 size_t rsort_topk_rows_workspace_size(int64_t rows, int64_t cols, int64_t k, int pairs) {
     return topk_rows_workspace_size(rows, cols, k, pairs ? 1 : 0);
@@ -1634,8 +1587,8 @@ int rsort_topk_rows_check(int64_t rows, int64_t cols, int64_t k, int pairs, cons
     if (!flags) return RSORT_ERR_ARG;
     *flags = 0;
     if (report4) memset(report4, 0, 4 * sizeof(int64_t));
-    if (!topk_rows_sizes_ok(rows, cols, k, &st)) return st;
-    if (rows == 0 || cols == 0 || k == 0) return RSORT_OK;
+    if ((st = topk_rows_sizes(rows, cols, k))) return st;
+    if (topk_rows_empty(rows, cols, k)) return RSORT_OK;
     if (!d_workspace) return RSORT_ERR_ARG;
     return topk_rows_read_check(rows, k, pairs ? 1 : 0, const_cast<void *>(d_workspace), flags, report4,
                                 (hipStream_t)stream);
@@ -1646,20 +1599,16 @@ int rsort_topk_rows_grids(int64_t rows, int64_t cols, int64_t k, int pairs, int 
     (void)pairs;  // (keys and pairs run the same kernels)
     if (!grids2) return RSORT_ERR_ARG;
     grids2[0] = grids2[1] = 0;
-    if (!topk_rows_sizes_ok(rows, cols, k, &st)) return st;
-    if (rows == 0 || cols == 0 || k == 0) return RSORT_OK;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return RSORT_ERR_NODEV;
+    if ((st = topk_rows_sizes(rows, cols, k))) return st;
+    if (topk_rows_empty(rows, cols, k)) return RSORT_OK;
+    if (!have_device()) return RSORT_ERR_NODEV;
     const int cls = topk_rows_class(cols);
     grids2[0] = (int)topk_rows_grid(rows, cls);
     grids2[1] = cls;
     return RSORT_OK;
 }
 
-int rsort_set_topk_rows_grid_limit(int workgroups) {
-    if (workgroups < 0) return -RSORT_ERR_ARG;
-    return g_topk_rows_grid_limit.exchange(workgroups);
-}
+int rsort_set_topk_rows_grid_limit(int workgroups) { return set_grid_limit(g_topk_rows_grid_limit, workgroups); }
 
 int rsort_pass_histogram(const rsort_plan *plan, const uint32_t *d_keys, int shift,
                          uint32_t *d_table, void *stream) {
@@ -1745,7 +1694,7 @@ int rsort_hybrid_range(int64_t *min_keys, int64_t *max_keys) {
 }
 
 int rsort_hybrid_gate_threshold(int64_t n) {
-    if (n <= 0 || n >= ((int64_t)1 << 32)) return -RSORT_ERR_SIZE;
+    if (n == 0 || !key_count_ok(n)) return -RSORT_ERR_SIZE;
     return (int)gate_threshold(n);
 }
 
@@ -1832,8 +1781,7 @@ size_t rsort_scatter_kernels_used(char *buf, size_t len, int reset) {
 size_t rsort_scatter_kernels_known(char *buf, size_t len) { return scatter_kernels_known(buf, len); }
 
 int rsort_lane_order_probe(void) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return -RSORT_ERR_NODEV;
+    if (!have_device()) return -RSORT_ERR_NODEV;
     return lane_order_probe();
 }
 
@@ -1982,7 +1930,7 @@ int rsort_top_histogram(const uint32_t *d_keys, int64_t n, int top_bits, uint32_
 int rsort_top_histogram_sampled(const uint32_t *d_keys, int64_t n, int top_bits, int stride, uint32_t *d_hist,
                                 void *stream) {
     if (top_bits < 1 || top_bits > kMaxBits) return RSORT_ERR_BITS;
-    if (n < 0 || n >= ((int64_t)1 << 32)) return RSORT_ERR_SIZE;
+    if (!key_count_ok(n)) return RSORT_ERR_SIZE;
     if (stride < 1 || !d_hist || (n > 0 && !d_keys)) return RSORT_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(d_hist, 0, ((size_t)1 << top_bits) * 4, s) != hipSuccess) return RSORT_ERR_HIP;
@@ -1993,7 +1941,7 @@ int rsort_top_histogram_sampled(const uint32_t *d_keys, int64_t n, int top_bits,
 
 int rsort_sample_device(const uint32_t *d_keys, int64_t n, int64_t stride, int64_t count, int64_t row_len,
                         uint32_t *d_out, void *stream) {
-    if (n < 0 || n >= ((int64_t)1 << 32)) return RSORT_ERR_SIZE;
+    if (!key_count_ok(n)) return RSORT_ERR_SIZE;
     if (stride < 1 || count < 0 || row_len < count || (row_len > 0 && !d_out) || (count > 0 && n > 0 && !d_keys))
         return RSORT_ERR_ARG;
     return hip_status(launch_sample(d_keys, (uint64_t)n, (uint64_t)stride, (uint64_t)count, (uint64_t)row_len, d_out,
@@ -2002,7 +1950,7 @@ int rsort_sample_device(const uint32_t *d_keys, int64_t n, int64_t stride, int64
 
 int rsort_fingerprint_device(const uint32_t *d_keys, const uint32_t *d_vals, int64_t n, uint64_t *d_out,
                              void *stream) {
-    if (n < 0 || n >= ((int64_t)1 << 32)) return RSORT_ERR_SIZE;
+    if (!key_count_ok(n)) return RSORT_ERR_SIZE;
     if (!d_out || (n > 0 && !d_keys)) return RSORT_ERR_ARG;
     return hip_status(launch_fingerprint(d_keys, d_vals, (uint64_t)n, (unsigned long long *)d_out, (hipStream_t)stream));
 }

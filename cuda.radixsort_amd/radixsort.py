@@ -296,6 +296,24 @@ def _check(status: int, where: str):
         raise RSortError(status, where)
 
 
+@contextmanager
+def _setting(setter: str, value, getter: str | None = None):
+    """A process-wide library setting for the block; the one before comes back on exit. The C setter returns the old
+    value, or -status where it refuses `value` (RSortError); one that returns a status instead comes with its getter."""
+    fn = getattr(_lib(), setter)
+    if getter is None:
+        old = int(fn(int(value)))
+        if old < 0:
+            raise RSortError(-old, setter)
+    else:
+        old = int(getattr(_lib(), getter)())
+        _check(fn(int(value)), setter)
+    try:
+        yield
+    finally:
+        fn(old)
+
+
 def version() -> str:
     v = _lib().rsort_version()
     return f"{v // 10000}.{v // 100 % 100}.{v % 100}"
@@ -436,14 +454,8 @@ def get_hybrid() -> int:
     return int(_lib().rsort_get_hybrid())
 
 
-@contextmanager
 def hybrid(mode: int):
-    old = get_hybrid()
-    set_hybrid(mode)
-    try:
-        yield
-    finally:
-        set_hybrid(old)
+    return _setting("rsort_set_hybrid", mode, "rsort_get_hybrid")
 
 
 def hybrid_capacity() -> int:
@@ -510,25 +522,15 @@ def plan_features(p: Plan) -> int:
     return f
 
 
-@contextmanager
 def table_fault():
     """TEST HOOK (rsort_inject_table_fault): raw-table sorts corrupt the table pass 1 reads."""
-    old = _lib().rsort_inject_table_fault(1)
-    try:
-        yield
-    finally:
-        _lib().rsort_inject_table_fault(old)
+    return _setting("rsort_inject_table_fault", 1)
 
 
-@contextmanager
 def rank_fault():
     """TEST HOOK (rsort_inject_rank_fault): the lane-ordered scatter kernels swap two ranks per digit in
     the slot their per-tile rank check reads (a broken lane order); the check must report it."""
-    old = _lib().rsort_inject_rank_fault(1)
-    try:
-        yield
-    finally:
-        _lib().rsort_inject_rank_fault(old)
+    return _setting("rsort_inject_rank_fault", 1)
 
 
 CHECK_TABLE, CHECK_RANK_ORDER = 1, 2
@@ -694,13 +696,8 @@ def set_multi_options(flags: int) -> int:
     return int(_lib().rsort_set_multi_options(int(flags)))
 
 
-@contextmanager
 def multi_options(flags: int):
-    old = set_multi_options(flags)
-    try:
-        yield
-    finally:
-        set_multi_options(old)
+    return _setting("rsort_set_multi_options", flags)
 
 
 def set_exchange_piece(keys: int) -> int:
@@ -879,24 +876,12 @@ def lane_order_probe() -> int:
     return r
 
 
-@contextmanager
 def rank_algo(algo: int):
-    old = get_rank_algo()
-    set_rank_algo(algo)
-    try:
-        yield
-    finally:
-        set_rank_algo(old)
+    return _setting("rsort_set_rank_algo", algo, "rsort_get_rank_algo")
 
 
-@contextmanager
 def group_chunks(enable: bool):
-    old = get_group_chunks()
-    set_group_chunks(enable)
-    try:
-        yield
-    finally:
-        set_group_chunks(old)
+    return _setting("rsort_set_group_chunks", bool(enable), "rsort_get_group_chunks")
 
 
 class Profile:
@@ -1032,17 +1017,10 @@ def segmented_grids(n: int, num_segments: int, pairs: bool = False) -> dict:
     return {k: int(g[i]) for i, k in enumerate(SEG_KERNELS)}
 
 
-@contextmanager
 def segmented_grid_limit(workgroups: int):
     """TEST HOOK (rsort_set_segmented_grid_limit): every segmented-sort kernel runs with at most `workgroups`
     workgroups, so each strides over its list; the previous setting comes back on exit."""
-    old = int(_lib().rsort_set_segmented_grid_limit(int(workgroups)))
-    if old < 0:
-        raise RSortError(-old, "rsort_set_segmented_grid_limit")
-    try:
-        yield
-    finally:
-        _lib().rsort_set_segmented_grid_limit(old)
+    return _setting("rsort_set_segmented_grid_limit", workgroups)
 
 
 def sortSegmentsByDevice(keys, offsets, out, vals=None, vals_out=None):
@@ -1107,16 +1085,9 @@ def get_topk_route() -> int:
     return int(_lib().rsort_get_topk_route())
 
 
-@contextmanager
 def topk_route(mode: int):
     """rsort_set_topk_route (process-wide) for the block: TOPK_AUTO, TOPK_SELECT or TOPK_SORT."""
-    old = int(_lib().rsort_set_topk_route(int(mode)))
-    if old < 0:
-        raise RSortError(-old, "rsort_set_topk_route")
-    try:
-        yield
-    finally:
-        _lib().rsort_set_topk_route(old)
+    return _setting("rsort_set_topk_route", mode)
 
 
 def topk_auto_limit(n: int, pairs: bool = False) -> int:
@@ -1136,17 +1107,10 @@ def topk_grids(n: int, k: int, pairs: bool = False) -> dict:
     return {name: int(g[i]) for i, name in enumerate(TOPK_KERNELS)}
 
 
-@contextmanager
 def topk_grid_limit(workgroups: int):
     """TEST HOOK (rsort_set_topk_grid_limit): every select kernel runs with at most `workgroups` workgroups, so
     each walks several tiles; the previous setting comes back on exit."""
-    old = int(_lib().rsort_set_topk_grid_limit(int(workgroups)))
-    if old < 0:
-        raise RSortError(-old, "rsort_set_topk_grid_limit")
-    try:
-        yield
-    finally:
-        _lib().rsort_set_topk_grid_limit(old)
+    return _setting("rsort_set_topk_grid_limit", workgroups)
 
 
 def topk_device(keys, k, largest=False, vals=None, indices=False, sorted=True, out=None, ws=None, stream=None):
@@ -1205,17 +1169,10 @@ def topk_rows_grids(rows: int, cols: int, k: int, pairs: bool = False) -> dict:
     return {"workgroups": int(g[0]), "kernel": int(g[1])}
 
 
-@contextmanager
 def topk_rows_grid_limit(workgroups: int):
     """TEST HOOK (rsort_set_topk_rows_grid_limit): the row-wise select runs with at most `workgroups` workgroups,
     so each strides over the rows; the previous setting comes back on exit."""
-    old = int(_lib().rsort_set_topk_rows_grid_limit(int(workgroups)))
-    if old < 0:
-        raise RSortError(-old, "rsort_set_topk_rows_grid_limit")
-    try:
-        yield
-    finally:
-        _lib().rsort_set_topk_rows_grid_limit(old)
+    return _setting("rsort_set_topk_rows_grid_limit", workgroups)
 
 
 def _rows_2d(t, name, shape=None):

@@ -11,6 +11,7 @@ partition) or, at 2^28 keys, the input's device fingerprint; check words must be
 runs of the library is "reports, flags and kernel names equal the zero-filled run's", on top of the oracle's.
 Runs on the MI355X box (-m gpu)."""
 import functools
+import threading
 from contextlib import ExitStack, contextmanager
 
 import numpy as np
@@ -504,9 +505,37 @@ def test_automatic_route_chain():
     step("uniform", 0x5EED)
 
 
+def topk_want(x, k, largest=False, vals=None, indices=False, sorted=True):
+    """numpy's statement of the top-k contract for every row of a 2-D x (include/rsort.h): the first k of the stable
+    argsort of key ^ m; unsorted, the same entries in column order (what the row-wise select writes)."""
+    m = np.uint32(0xFFFFFFFF if largest else 0)
+    idx = np.argsort(x ^ m, axis=1, kind="stable")[:, :k]
+    if not sorted:
+        idx = np.sort(idx, axis=1)
+    wv = idx.astype(np.uint32) if indices else None if vals is None else np.take_along_axis(vals, idx, 1)
+    return np.take_along_axis(x, idx, 1), wv
+
+
+def check_host_topk(x, k, **kw):
+    gk, gv = rs.topkByDevice(x, k, **kw)
+    wk, wv = topk_want(x[None, :], k, **kw)
+    assert np.array_equal(gk, wk[0]) and (gv is None) == (wv is None), (x.size, k, kw)
+    assert wv is None or np.array_equal(gv, wv[0]), (x.size, k, kw)
+
+
+def check_host_topk_rows(x, rows, cols, k, vals=False, **kw):
+    mat = np.resize(x, rows * cols).reshape(rows, cols)  # (the keys again from the start where x is shorter)
+    v = (np.arange(rows * cols, dtype=np.uint32) * np.uint32(3)).reshape(rows, cols) if vals else None
+    gk, gv = rs.topkRowsByDevice(mat, k, vals_2d=v, **kw)
+    wk, wv = topk_want(mat, k, vals=v, **kw)
+    assert np.array_equal(gk, wk) and (gv is None) == (wv is None), (x.size, rows, cols, k, kw)
+    assert wv is None or np.array_equal(gv, wv), (x.size, rows, cols, k, kw)
+
+
 def test_host_entries_share_the_cached_buffer():
     """The host entries carve one cached device buffer differently for every (n, k, pairs): sizes that shrink and
-    grow, each call against the oracle (a non-zero status -- the check word among them -- raises)."""
+    grow, each call against the oracle (a non-zero status -- the check word among them -- raises). The top-k entries
+    between the sorts put regions of k entries and their own workspaces into the same buffer."""
     for n, k in zip((70001, 1 << 20, 513, 250001), (8, 4, 5, 12)):
         x = uniform_keys(n, seed=n)
         v = np.arange(n, dtype=np.uint32)
@@ -514,19 +543,64 @@ def test_host_entries_share_the_cached_buffer():
         out = np.zeros_like(x)
         rs.sortByDevice(x, n, out, k)
         assert np.array_equal(out, want), (n, k)
+        check_host_topk(x, n // 7, largest=True)
         ko, vo = np.zeros_like(x), np.zeros_like(v)
         rs.sortPairsByDevice(x, v, n, ko, vo, k)
         wk, wv = oracle_sort_pairs(x, v, k)
         assert np.array_equal(ko, wk) and np.array_equal(vo, wv), (n, k)
+        check_host_topk_rows(x, 37, 300, 17)
         lengths = [n // 5, 0, 1, n // 3, min(300, n // 8), 64 if n > 1000 else 5]
         off = _offsets(lengths + [n - sum(lengths) - 7], start=3)
         ko, vo = np.zeros_like(x), np.zeros_like(v)
         rs.sortSegmentsByDevice(x, off, ko, vals=v, vals_out=vo)
         ek, ev = _expected(x, v, off)
         assert np.array_equal(ko, ek) and np.array_equal(vo, ev), n
+        check_host_topk(x, n // 7, indices=True)
+        check_host_topk_rows(x, 5, 20000, 17, vals=True, largest=True, sorted=False)
         out = np.zeros_like(x)
         rs.sortByDevice(x, n, out, k)
         assert np.array_equal(out, want), (n, k)
+
+
+def test_host_entries_hold_the_cache_lock():
+    """Two threads, four host calls each on the one cached buffer of the device (ctypes releases the GIL): the sorts
+    in one, the top-k entries in the other. An entry that let go of the cache's lock before its last copy had
+    landed would have its regions overwritten by the other thread's call."""
+    n = 1 << 18
+    x = zipf_keys(n, seed=7)
+    v = np.arange(n, dtype=np.uint32)
+    off = _offsets([n // 3, 0, 5000, n // 2, 77], start=11)
+    sort_want, seg_want = oracle_sort(x, 8), _expected(x, v, off)
+    errors = []
+
+    def sorts():
+        for _ in range(2):
+            out = np.zeros_like(x)
+            rs.sortByDevice(x, n, out, 8)
+            assert np.array_equal(out, sort_want)
+            ko, vo = np.zeros_like(x), np.zeros_like(v)
+            rs.sortSegmentsByDevice(x, off, ko, vals=v, vals_out=vo)
+            assert np.array_equal(ko, seg_want[0]) and np.array_equal(vo, seg_want[1])
+
+    def topks():
+        for largest in (False, True):
+            check_host_topk(x, n // 7, largest=largest, indices=True)
+            check_host_topk_rows(x, 64, 4096, 17, vals=True, largest=largest)
+
+    def guarded(fn):
+        def run():
+            try:
+                fn()
+            except BaseException as e:  # noqa: BLE001 -- reported by the test's own thread
+                errors.append((fn.__name__, repr(e)))
+        return threading.Thread(target=run)
+
+    threads = [guarded(sorts), guarded(topks)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not errors, errors
 
 
 # ------------------------------------------------------------------------------ 3. graph replay

@@ -7,7 +7,11 @@ A plan without explicit tiles_per_chunk sizes its chunks from an occupancy query
 sizes are computed in one child process that sees no device (chunks from the 256-CU, 2-workgroup default).
 
 walk() below restates the layout from DESIGN §3 "Workspace state" on its own: every size must also equal it. For a
-partition that is the point -- its plan has no next-digit tables, whatever its bucket bits."""
+partition that is the point -- its plan has no next-digit tables, whatever its bucket bits.
+
+The families `segmented`, `topk` and `topk_rows` (rsort_segmented_workspace_size, rsort_topk_workspace_size with the
+route given, rsort_topk_rows_workspace_size) were recorded the same way from the commit before those three layouts
+and the sort's became walks over one allocator; seg_walk() and rows_walk() restate the two simple ones."""
 import json
 import os
 import subprocess
@@ -24,6 +28,10 @@ MULTI_WORLD = 8
 # chunks, raw next-digit tables; at 2^23 + 9: 2049, tail scans), and 256 chunks where n has the tiles for them
 # (k = 8 on line tiles: the digit-group plans)
 MODES = ("auto", "one", "c256")
+SEG_NSEGS = (0, 1, 1000, 1 << 20, (1 << 31) - 1)
+TOPK_NS = (0, 1, 63, 70001, 1 << 20, (1 << 24) + 3, 1 << 30, (1 << 32) - 1)
+TOPK_ROUTES = ("select", "sort")  # rs.TOPK_SELECT, rs.TOPK_SORT = 1, 2
+ROWS_SHAPES = ((1, 1), (4, 64), (1000, 300), (1 << 20, 64), (4096, 16384), (3, 1 << 30))
 
 
 def al(x):
@@ -39,12 +47,20 @@ def tiles_per_chunk(rs, n, k, pairs, mode):
     return max(1, -(-max(1, -(-n // tile)) // 256))
 
 
+def topk_ks(n):
+    return (0, min(n, 64), n // 3, n)
+
+
+def rows_ks(cols):
+    return (1, cols // 4, cols)
+
+
 def compute():
     """Every size of the grid, from the library as built (run where no device is visible)."""
     sys.path.insert(0, str(Path(__file__).resolve().parent))
     from _rs import rs
     lib = rs._lib()
-    out = {"sort": {}, "plans": {}, "partition": {}, "multi": {}}
+    out = {"sort": {}, "plans": {}, "partition": {}, "multi": {}, "segmented": {}, "topk": {}, "topk_rows": {}}
     for k in KS:
         for pairs in (0, 1):
             for mode in MODES:
@@ -63,6 +79,16 @@ def compute():
             out["multi"][f"k{k} {'pairs' if pairs else 'keys'}"] = [
                 int(lib.rsort_multi_workspace_size(n, rs.default_capacity(n), k, pairs, MULTI_WORLD))
                 for n in MULTI_NS]
+    for pairs in (0, 1):
+        kind = "pairs" if pairs else "keys"
+        for nseg in SEG_NSEGS:
+            out["segmented"][f"nseg{nseg} {kind}"] = [rs.segmented_workspace_size(n, nseg, bool(pairs)) for n in NS]
+        # (the finishing sort's plan sizes its chunks like any sort's: from the occupancy where a device is present)
+        for route, name in enumerate(TOPK_ROUTES, start=rs.TOPK_SELECT):
+            out["topk"][f"{name} {kind}"] = [[rs.topk_workspace_size(n, k, bool(pairs), route) for k in topk_ks(n)]
+                                             for n in TOPK_NS]
+        out["topk_rows"][kind] = [[rs.topk_rows_workspace_size(rows, cols, k, bool(pairs)) for k in rows_ks(cols)]
+                                  for rows, cols in ROWS_SHAPES]
     return out
 
 
@@ -141,6 +167,28 @@ SIZES = {
         "k4 keys": [76029952, 76030208, 76430080, 76685568, 92807424, 113861120, 151619328, 92807168, 642355968, 9702054912],
         "k4 pairs": [76029952, 76030464, 76830208, 77341184, 114068736, 189565952, 265065728, 114067456, 1246533888, 19365927936],
     },
+    "segmented": {
+        "nseg0 keys": [256, 512, 400384, 655872, 16777728, 33554944, 50331904, 16777472, 268435712, 4294967552, 17179869440],
+        "nseg1 keys": [1280, 1536, 401408, 656896, 16778752, 33555968, 50332928, 16778496, 268436736, 4294968576, 17179870464],
+        "nseg1000 keys": [16640, 16896, 416768, 672256, 16794112, 33571328, 50348288, 16793856, 268452096, 4294983936, 17179885824],
+        "nseg1048576 keys": [16777472, 16777728, 17177600, 17433088, 33554944, 50332160, 67109120, 33554688, 285212928, 4311744768, 17196646656],
+        "nseg2147483647 keys": [34359738624, 34359738880, 34360138752, 34360394240, 34376516096, 34393293312, 34410070272, 34376515840, 34628174080, 38654705920, 51539607808],
+        "nseg0 pairs": [256, 768, 800512, 1311488, 33555200, 67109632, 100663552, 33554688, 536871168, 8589934848, 34359738624],
+        "nseg1 pairs": [1280, 1792, 801536, 1312512, 33556224, 67110656, 100664576, 33555712, 536872192, 8589935872, 34359739648],
+        "nseg1000 pairs": [16640, 17152, 816896, 1327872, 33571584, 67126016, 100679936, 33571072, 536887552, 8589951232, 34359755008],
+        "nseg1048576 pairs": [16777472, 16777984, 17577728, 18088704, 50332416, 83886848, 117440768, 50331904, 553648384, 8606712064, 34376515840],
+        "nseg2147483647 pairs": [34359738624, 34359739136, 34360538880, 34361049856, 34393293568, 34426848000, 34460401920, 34393293056, 34896609536, 42949673216, 68719476992],
+    },
+    "topk": {
+        "select keys": [[2150656, 2150656, 2150656, 2150656], [2150912, 2151424, 2150912, 2151424], [2150912, 2151424, 2151424, 2151424], [2430720, 2431232, 2622720, 3008256], [6344960, 6345472, 9228544, 14994688], [69259776, 69260288, 114465280, 203827200], [4297117952, 4297118464, 7160950016, 12887575808], [17182019840, 17182020352, 28635789568, 51542281472]],
+        "sort keys": [[3328, 3328, 3328, 3328], [3840, 3840, 3840, 3840], [3840, 3840, 3840, 3840], [580864, 580864, 580864, 580864], [8653056, 8653056, 8653056, 8653056], [134570752, 134570752, 134570752, 134570752], [8590461184, 8590461184, 8590461184, 8590461184], [34360264960, 34360264960, 34360264960, 34360264960]],
+        "select pairs": [[2150656, 2150656, 2150656, 2150656], [2151168, 2152192, 2151168, 2152192], [2151168, 2152192, 2152192, 2152192], [2710784, 2711808, 3089664, 3848448], [10539264, 10540288, 16219392, 27577600], [136368896, 136369920, 226197248, 405224192], [8592085248, 8592086272, 14319229184, 25772477696], [34361889024, 34361890048, 57268905216, 103081889024]],
+        "sort pairs": [[3328, 3328, 3328, 3328], [4352, 4352, 4352, 4352], [4352, 4352, 4352, 4352], [1140992, 1140992, 1140992, 1140992], [17041664, 17041664, 17041664, 17041664], [268858624, 268858624, 268858624, 268858624], [17180395776, 17180395776, 17180395776, 17180395776], [68720003328, 68720003328, 68720003328, 68720003328]],
+    },
+    "topk_rows": {
+        "keys": [[2304, 2048, 2304], [2304, 2304, 3072], [25344, 321280, 1221376], [25166848, 88081408, 289408000], [99328, 67191808, 268518400], [2304, 3221227520, 12884903936]],
+        "pairs": [[2560, 2048, 2560], [2560, 2560, 4096], [29440, 621312, 2421504], [29361152, 155190272, 557843456], [115712, 134300672, 536953856], [2560, 6442452992, 25769805824]],
+    },
 }
 
 
@@ -187,6 +235,22 @@ def partition_shape(n, nb, pairs):
     tiles = max(1, -(-n // tile))
     tpc = -(-tiles // 512)
     return 1 << bits, -(-tiles // tpc)
+
+
+SEG_KINDS = 4  # one list per kernel kind of the segmented sort, room for every segment in each
+
+
+def seg_walk(n, nseg, pairs):
+    b = al(4 * n) * (2 if pairs else 1)        # the multi-tile path's ping-pong keys (and values)
+    b += SEG_KINDS * al(4 * nseg)              # the kinds' segment lists
+    return b + 256                             # counters and check word
+
+
+def rows_walk(rows, k, pairs):
+    b = 256                                    # state words
+    b += al(4 * (rows + 1))                    # the finishing sort's offsets
+    b += seg_walk(rows * k, rows, pairs)       # the segmented sort of rows segments of k entries
+    return b + 256                             # slack: the regions start at the caller's pointer rounded up to 256
 
 
 # ------------------------------------------------------------------------------ tests
@@ -236,13 +300,41 @@ def test_multi_workspace_sizes_unchanged():
         assert got[key] == want, key
 
 
+def test_segmented_workspace_sizes_unchanged_and_the_walk():
+    got = computed()["segmented"]
+    assert set(got) == set(SIZES["segmented"])
+    for key, want in SIZES["segmented"].items():
+        assert got[key] == want, key
+        nseg, pairs = int(key.split()[0][4:]), key.endswith("pairs")
+        for n, size in zip(NS, got[key]):
+            assert size == seg_walk(n, nseg, pairs), (key, n)
+
+
+def test_topk_workspace_sizes_unchanged():
+    got = computed()["topk"]
+    assert set(got) == set(SIZES["topk"])
+    for key, want in SIZES["topk"].items():
+        assert got[key] == want, key
+        assert all(size > 0 for row in got[key] for size in row), key  # (0 is the entry's "bad arguments")
+
+
+def test_topk_rows_workspace_sizes_unchanged_and_the_walk():
+    got = computed()["topk_rows"]
+    assert set(got) == set(SIZES["topk_rows"])
+    for key, want in SIZES["topk_rows"].items():
+        assert got[key] == want, key
+        for (rows, cols), row in zip(ROWS_SHAPES, got[key]):
+            for k, size in zip(rows_ks(cols), row):
+                assert size == rows_walk(rows, k, key == "pairs"), (key, rows, cols, k)
+
+
 if __name__ == "__main__":
     res = compute()
     if "--json" in sys.argv:
         print(json.dumps(res))
     else:  # the literal above
         print("SIZES = {")
-        for fam in ("sort", "partition", "multi"):
+        for fam in ("sort", "partition", "multi", "segmented", "topk", "topk_rows"):
             print(f'    "{fam}": {{')
             for key, row in res[fam].items():
                 print(f'        "{key}": {row},')
