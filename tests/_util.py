@@ -183,5 +183,111 @@ def fingerprint_ref(keys: np.ndarray, vals: np.ndarray | None = None) -> tuple[i
     return h, descents
 
 
+# ----------------------------------------------------------------------------- top-k of a periodic input
+def periodic_topk_tables(base: np.ndarray, n: int, largest: bool) -> dict:
+    """The input x[i] = base[i % P] (P = base.size, i < n) by the distinct values of base ^ m, ascending (m = 0xFFFFFFFF
+    for the k largest, else 0) -- int64 arrays, one entry per distinct value ("group") unless said otherwise:
+    gx the value, gsize its base positions, goff where they start in ps, gcount its copies in x (a base position p has
+    (n - 1 - p) // P + 1 of them, none at p >= n), gstart / gend the copies before it / through it; ps (P entries): the
+    base positions by (value, position); copies (P entries): the copies by base position. Never touches n elements."""
+    base = np.ascontiguousarray(base, dtype=np.uint32)
+    P, n = int(base.size), int(n)
+    assert P >= 1 and 0 <= n < (1 << 32)
+    m = np.uint32(0xFFFFFFFF if largest else 0)
+    xb = base ^ m
+    p = np.arange(P, dtype=np.int64)
+    copies = np.where(p < n, (n - 1 - p) // P + 1, 0).astype(np.int64)
+    ps = np.argsort(xb, kind="stable").astype(np.int64)  # by (value, position)
+    xs = xb[ps]
+    goff = np.flatnonzero(np.r_[True, xs[1:] != xs[:-1]]).astype(np.int64)
+    gcount = np.add.reduceat(copies[ps], goff).astype(np.int64)
+    gend = np.cumsum(gcount)
+    return {"P": P, "n": n, "m": int(m), "xb": xb, "copies": copies, "ps": ps, "gx": xs[goff].astype(np.int64),
+            "goff": goff, "gsize": np.diff(np.r_[goff, P]).astype(np.int64), "gcount": gcount, "gstart": gend - gcount,
+            "gend": gend}
+
+
+PERIODIC_POSITION_TABLES = ("gend", "gstart", "gsize", "goff", "ps")  # what periodic_topk_positions reads, with "P"
+
+
+def periodic_topk_positions(tab: dict, ranks):
+    """(positions, groups) of the entries at `ranks` (int64, each < n) of the stable ascending order of x ^ m. A
+    value's base positions ps (ascending) stand in x at ps + P t: ordered by (t, p) and cut at n, its r-th copy is
+    ps[r % |ps|] + P (r // |ps|) -- every t below n // P has all of ps, the last one a prefix of it. Written once for
+    numpy arrays and for torch tensors (tab's PERIODIC_POSITION_TABLES then tensors on ranks' device): a k too large
+    for the host is expanded on the device in pieces by the same lines."""
+    if isinstance(ranks, np.ndarray):
+        g = np.searchsorted(tab["gend"], ranks, side="right")  # (a value without a copy, n < P, holds no rank)
+    else:
+        import torch
+        g = torch.searchsorted(tab["gend"], ranks, right=True)
+    r = ranks - tab["gstart"][g]
+    size = tab["gsize"][g]
+    return tab["ps"][tab["goff"][g] + r % size] + tab["P"] * (r // size), g
+
+
+def periodic_topk_expected(base: np.ndarray, n: int, k: int, largest: bool):
+    """The top-k contract for x[i] = base[i % P], i < n, in closed form: (keys, positions) of the first k entries of
+    the stable ascending order of x ^ m; keys uint32, positions int64 (they pass 2^31)."""
+    tab = periodic_topk_tables(base, n, largest)
+    assert 0 <= k <= tab["n"]
+    pos, g = periodic_topk_positions(tab, np.arange(k, dtype=np.int64))
+    return (tab["gx"][g] ^ tab["m"]).astype(np.uint32), pos
+
+
+def periodic_topk_report(base: np.ndarray, n: int, k: int, largest: bool) -> dict:
+    """rs.topk_report's fields on the SELECT route for the same input, from base and the copy counts alone."""
+    tab = periodic_topk_tables(base, n, largest)
+    assert 1 <= k <= tab["n"]
+    g = int(np.searchsorted(tab["gend"], k - 1, side="right"))
+    t = int(tab["gx"][g])
+    before = int(tab["gstart"][g])
+    top = (tab["xb"] >> np.uint32(24)) == np.uint32(t >> 24)
+    return {"kth_key": t ^ tab["m"], "before": before, "equal_taken": k - before,
+            "equal_in_input": int(tab["gcount"][g]), "candidates": int(tab["copies"][top].sum())}
+
+
+# ----------------------------------------------------------------------------- row-wise top-k: the select's exits
+TOPK_ROWS_CLASS_COLS = {0: 100, 1: 600, 2: 5000, 3: 20000}  # one row length inside each kernel class (wave .. stream)
+
+
+def select_exit_level(x_row: np.ndarray, k: int) -> int:
+    """The control flow of the row-wise select's four-level loop (csrc/rsort_topk_rows.hip) for a row of x = key ^ m:
+    per level the candidates' 8-bit digits are counted, the digit holding the krem-th is picked, rem = krem - (the
+    entries below it), and the loop stops with that level when the digit holds exactly rem. 0..3, or 4: ran through."""
+    cand, krem = np.ascontiguousarray(x_row, dtype=np.uint32), int(k)
+    assert 1 <= krem <= cand.size
+    for level in range(4):
+        digit = (cand >> np.uint32(24 - 8 * level)) & np.uint32(255)
+        cnt = np.bincount(digit, minlength=256)
+        cum = np.cumsum(cnt)
+        d = int(np.searchsorted(cum, krem, side="left"))  # the first digit with cum >= krem
+        rem = krem - int(cum[d] - cnt[d])
+        if int(cnt[d]) == rem:
+            return level
+        cand, krem = cand[digit == d], rem
+    return 4
+
+
+def byte_row(cols: int, level: int, seed: int) -> np.ndarray:
+    """A row in which only the byte of one select level varies (bits 24 - 8 level and the 7 above), over 16 digit
+    values in a seeded order, each held by cols // 16 entries or one more (cols >= 32: at least two); the other three
+    bytes are constants. k at a cumulative digit count then ends the select at that level, one more runs through all
+    four levels (the next digit holds more than the one entry wanted and no lower byte separates), k = cols ends at
+    level 0; the same in x = key ^ 0xFFFFFFFF, where the digits' order turns round."""
+    assert cols >= 32 and 0 <= level <= 3
+    sh = np.uint32(24 - 8 * level)
+    which = np.argsort(uniform_keys(cols, seed=seed), kind="stable") % 16  # a seeded permutation: balanced counts
+    digit = (np.uint32(9) + np.uint32(15) * which.astype(np.uint32)) << sh  # 9, 24, .. 234
+    return (np.uint32(0x5AC3A53C) & ~(np.uint32(255) << sh)) | digit
+
+
+def digit_boundaries(x_row: np.ndarray, level: int) -> np.ndarray:
+    """The cumulative counts of the level's digits of x_row, ascending: the ks at which a byte_row's select stops."""
+    x = np.ascontiguousarray(x_row, dtype=np.uint32)
+    cnt = np.bincount((x >> np.uint32(24 - 8 * level)) & np.uint32(255), minlength=256)
+    return np.cumsum(cnt[cnt > 0])
+
+
 def env_flag(name: str) -> bool:
     return os.environ.get(name, "") not in ("", "0", "false", "False")

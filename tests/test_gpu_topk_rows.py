@@ -12,14 +12,15 @@ import numpy as np
 import pytest
 
 from _rs import rs
-from _util import oracle_sort_pairs, uniform_keys, zipf_keys
+from _util import (TOPK_ROWS_CLASS_COLS, byte_row, digit_boundaries, oracle_sort_pairs, select_exit_level, uniform_keys,
+                   zipf_keys)
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 MODES = ("keys", "vals", "indices")
 WAVE, SMALL, LDS, STREAM = range(4)
-CLASS_COLS = {WAVE: 100, SMALL: 600, LDS: 5000, STREAM: 20000}  # one row length inside each kernel class
+CLASS_COLS = TOPK_ROWS_CLASS_COLS  # {WAVE: 100, SMALL: 600, LDS: 5000, STREAM: 20000}: one row length inside each class
 KNOWN_SCATTER_KERNELS = 144  # len(rs.scatter_kernels_known()) of the parent commit: this feature adds none
 SENTINEL = 0x5A5A5A5A
 PAD = 64
@@ -58,6 +59,8 @@ def _row(name, cols, r):
         return np.full(cols, 0xFFFFFFFF if r & 1 else 0, np.uint32)
     if name == "steps":  # every row's keys lie in a band of its own, so the rows' k-th keys all differ
         return (uniform_keys(cols, seed=21 + r) >> np.uint32(8)) + np.uint32((r * 37 % 251) << 24)
+    if name in ("byte0", "byte1", "byte2", "byte3"):  # only the byte of one select level varies (tests/_util.py)
+        return byte_row(cols, int(name[4]), seed=40 + r)
     raise KeyError(name)
 
 
@@ -391,6 +394,100 @@ def test_finishing_sort_is_the_segmented_sort(cols, k, seg_class):
     base = -ws.data_ptr() % 256 + 256 + (4 * (rows + 1) + 255) // 256 * 256
     flags, counts = rs.segmented_check(rows * k, rows, pairs, ws[base:])
     assert flags == 0 and counts[seg_class] == rows and sum(counts.values()) == rows, counts
+
+
+# ------------------------------------------------------------------------------ every exit of the select
+@pytest.mark.parametrize("cls", (WAVE, SMALL, LDS, STREAM))
+def test_select_exit_levels(cls):
+    """The four-level loop leaves at the first level whose picked digit holds exactly what is wanted, and entries are
+    then compared by the chosen upper bits alone. Rows in which only one level's byte varies (byte_row) put the exit
+    where the test wants it: k at a digit boundary ends at that level, one more runs through all four, k = cols ends at
+    level 0. The host model (select_exit_level) says so for every row and k before anything runs, and that the class
+    sees every exit: 0, 1, 2, 3 and the run through (4)."""
+    cols, rows = CLASS_COLS[cls], 3
+    cases, seen, at_level_2 = [], set(), {}
+    for level in range(4):
+        name = "byte%d" % level
+        x = matrix(name, rows, cols)
+        for largest in (False, True):
+            m = np.uint32(0xFFFFFFFF if largest else 0)
+            bounds = digit_boundaries(x[0] ^ m, level)
+            near = int(bounds[np.argmin(np.abs(bounds - cols // 3))])  # the digit boundary nearest cols // 3 of row 0
+            for k, want in ((near, level), (near + 1, 4), (cols, 0)):
+                exits = {select_exit_level(x[r] ^ m, k) for r in range(rows)}
+                assert exits == {want}, (cls, level, largest, k, exits)
+                seen |= exits
+                cases.append((name, k, largest))
+            if level == 2:
+                at_level_2[largest] = near
+    assert seen == {0, 1, 2, 3, 4}
+    for name, k, largest in cases:
+        for mode in ("keys", "indices"):
+            check_case(name, rows, cols, k, largest, mode)
+    for largest, k in at_level_2.items():  # the raw path writes x ^ m of entries compared by 16 bits only
+        check_case("byte2", rows, cols, k, largest, "vals", sorted=False)
+
+
+# ------------------------------------------------------------------------------ past 2^31
+BASE_ROWS = 61
+PIECE = 1 << 26
+PAST_2_31 = (1 << 31) + (1 << 17)
+FULLSIZE = {  # class: cols, rows, k, the calls (mode, largest, sorted)
+    WAVE: (65, PAST_2_31 // 65 + 1, 3, (("indices", True, True), ("keys", False, False))),
+    LDS: (5000, PAST_2_31 // 5000 + 1, 65, (("indices", False, True),)),
+    SMALL: (1024, (1 << 21) + 4099, 1023, (("vals", False, True), ("indices", True, True))),
+    STREAM: (20001, PAST_2_31 // 20001 + 1, 70, (("vals", False, True),)),
+}
+
+
+def periodic_rows(base, rows):
+    """The rows x cols device matrix whose row r is base[r % 61] (base: 61 x cols on the device), built in pieces."""
+    cols = base.shape[1]
+    out = torch.empty((rows, cols), dtype=torch.int32, device="cuda")
+    step = max(1, PIECE // cols)
+    for r0 in range(0, rows, step):
+        r1 = min(rows, r0 + step)
+        out[r0:r1] = base.index_select(0, torch.arange(r0, r1, device="cuda") % BASE_ROWS)
+    return out
+
+
+@pytest.mark.parametrize("cls", (WAVE, SMALL, LDS, STREAM))
+def test_rows_past_2_31(cls):
+    """One shape per kernel whose last row starts at or above element 2^31 of the input (rows * cols < 2^32 is what
+    the entry accepts): row r = base_rows[r % 61], so the oracle's answer for 61 rows is every row's. The small-class
+    shape has k = 1023 of 1024 columns: its output, the i * k offsets and the finishing segmented sort pass 2^31
+    too. Compared on the device, bit for bit, in pieces of rows; the call's check must be clean."""
+    cols, rows, k, calls = FULLSIZE[cls]
+    assert cls_of(cols) == cls and (rows - 1) * cols >= 1 << 31 and rows * cols < 1 << 32
+    if cls == SMALL:
+        assert (rows - 1) * k >= 1 << 31
+    xb = np.ascontiguousarray(np.stack([_row(("zipf", "uniform", "steps")[r % 3], cols, r) for r in range(BASE_ROWS)]),
+                              dtype=np.uint32)
+    vb = uniform_keys(BASE_ROWS * cols, seed=0xBEEF).reshape(BASE_ROWS, cols)  # (never the positions)
+    d_x = periodic_rows(dev(xb), rows)
+    d_v = periodic_rows(dev(vb), rows) if any(mode == "vals" for mode, _, _ in calls) else None
+    step = max(1, PIECE // k)
+    for mode, largest, sorted_ in calls:
+        what = (cls, mode, largest, sorted_)
+        wk, wv = expected_from(xb, vb, row_order(xb, largest), k, mode)
+        ko, vo, ws = call(d_x, k, largest, mode, d_v, sorted_)
+        assert ko.shape == (rows, k) and (vo is None) == (wv is None), what
+        assert_clean(rows, cols, k, mode != "keys", ws, what)
+        del ws
+        ek, ev = dev(wk), None if wv is None else dev(wv)
+        if not sorted_:  # keys only: every row's entries in any order
+            assert wv is None
+            ek = torch.sort(ek.to(torch.int64) & 0xFFFFFFFF, dim=1).values
+        for r0 in range(0, rows, step):
+            r1 = min(rows, r0 + step)
+            src = torch.arange(r0, r1, device="cuda") % BASE_ROWS
+            got = ko[r0:r1] if sorted_ else torch.sort(ko[r0:r1].to(torch.int64) & 0xFFFFFFFF, dim=1).values
+            bad = (got != ek.index_select(0, src)).any(dim=1)
+            assert not bool(bad.any()), (what, "rows", (r0 + torch.nonzero(bad)[:8, 0]).tolist())
+            if ev is not None:
+                bad = (vo[r0:r1] != ev.index_select(0, src)).any(dim=1)
+                assert not bool(bad.any()), (what, "value rows", (r0 + torch.nonzero(bad)[:8, 0]).tolist())
+        del ko, vo
 
 
 # ------------------------------------------------------------------------------ unchanged behaviour

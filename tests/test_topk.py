@@ -4,8 +4,11 @@ import ctypes
 
 import numpy as np
 import pytest
+import torch
 
 from _rs import gpu_available, rs
+from _util import (PERIODIC_POSITION_TABLES, oracle_sort_pairs, periodic_topk_expected, periodic_topk_positions,
+                   periodic_topk_report, periodic_topk_tables, uniform_keys)
 
 P = ctypes.c_void_p
 BIG = 1 << 40
@@ -198,3 +201,61 @@ def test_report_entry_validates():
 def test_python_constants():
     assert (rs.TOPK_LARGEST, rs.TOPK_UNSORTED, rs.TOPK_INDICES) == (1, 2, 4)
     assert (rs.TOPK_AUTO, rs.TOPK_SELECT, rs.TOPK_SORT) == (0, 1, 2)
+
+
+# ------------------------------------------------------------------------------ the periodic input's closed form
+def _periodic_bases(period):
+    """A base of P distinct keys and one with long runs of duplicates (values below 5, and 0xFFFFFFFF among them)."""
+    distinct = uniform_keys(period, seed=0xA11 + period)
+    assert np.unique(distinct).size == period
+    dup = (uniform_keys(period, seed=0xD0 + period) % np.uint32(5)).astype(np.uint32)
+    dup[dup == 4] = 0xFFFFFFFF
+    return (("distinct", distinct), ("dup", dup))
+
+
+@pytest.mark.parametrize("period", (7, 13, 50, 97, 101))
+def test_periodic_topk_closed_form_matches_the_oracle(period):
+    """tests/_util.py periodic_topk_expected / periodic_topk_report (what the full-size GPU tests expect) against the
+    oracle's stable order and host counting on the materialised x: n below, at and far above P, bases with and
+    without duplicates, both directions, k in {1, 2, n // 3, n - 1, n}; the torch statement of the positions too."""
+    for kind, base in _periodic_bases(period):
+        for n in (1, 2, period - 1, period, period + 1, 3 * period, 1000, 4999, 5000):
+            x = base[np.arange(n) % period]
+            for largest in (False, True):
+                m = np.uint32(0xFFFFFFFF if largest else 0)
+                ko, idx = oracle_sort_pairs(x ^ m, np.arange(n, dtype=np.uint32), 8)
+                tab = periodic_topk_tables(base, n, largest)
+                tt = {f: torch.from_numpy(tab[f]) for f in PERIODIC_POSITION_TABLES}
+                tt["P"] = period
+                for k in sorted({min(max(k, 1), n) for k in (1, 2, n // 3, n - 1, n)}):
+                    what = (kind, period, n, largest, k)
+                    keys, pos = periodic_topk_expected(base, n, k, largest)
+                    assert keys.dtype == np.uint32 and pos.dtype == np.int64, what
+                    assert np.array_equal(pos, idx[:k]), what
+                    assert np.array_equal(keys, ko[:k] ^ m) and np.array_equal(keys, x[idx[:k]]), what
+                    tpos, _ = periodic_topk_positions(tt, torch.arange(k, dtype=torch.int64))
+                    assert np.array_equal(tpos.numpy(), pos), what
+                    kth = x[idx[k - 1]]  # host_report-style counting (tests/test_gpu_topk.py)
+                    t = kth ^ m
+                    before = int(np.count_nonzero((x ^ m) < t))
+                    want = {"kth_key": int(kth), "before": before, "equal_taken": k - before,
+                            "equal_in_input": int(np.count_nonzero(x == kth)),
+                            "candidates": int(np.count_nonzero(((x ^ m) >> np.uint32(24)) == (t >> np.uint32(24))))}
+                    assert periodic_topk_report(base, n, k, largest) == want, what
+
+
+def test_periodic_topk_closed_form_never_touches_n_elements():
+    """The full-size shape: n past 2^31, P = 4099, k = 2^20 -- well under a second, positions past 2^31 in int64."""
+    import time
+    n, k = (1 << 31) + (1 << 17) + 5, 1 << 20
+    base = uniform_keys(4099, seed=0xA11)  # distinct: two whole keys' copies, spread over the input, are taken
+    t0 = time.perf_counter()
+    keys, pos = periodic_topk_expected(base, n, k, True)
+    rep = periodic_topk_report(base, n, k, True)
+    took = time.perf_counter() - t0
+    assert took < 1.0, took
+    assert keys.size == pos.size == k and int(pos.max()) >= 1 << 31 and int(pos.max()) < n
+    assert np.array_equal(keys, base[pos % 4099]) and bool((np.diff(keys.astype(np.int64)) <= 0).all())
+    same = keys[1:] == keys[:-1]
+    assert bool((np.diff(pos)[same] > 0).all())  # equal keys in input order
+    assert rep["before"] + rep["equal_taken"] == k and rep["before"] >= 2 * (n // 4099)

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from _rs import gpu_available, rs
+from _util import TOPK_ROWS_CLASS_COLS, byte_row, digit_boundaries, select_exit_level
 
 P = ctypes.c_void_p
 BIG = 1 << 40
@@ -241,3 +242,42 @@ class _NoStream:
 
 def test_python_constants():
     assert rs.TOPK_ROWS_KERNELS == ("wave", "small", "lds", "stream")
+
+
+# ------------------------------------------------------------------------------ the select's exits, by construction
+@pytest.mark.parametrize("cls", sorted(TOPK_ROWS_CLASS_COLS))
+def test_byte_rows_reach_every_exit_of_the_select(cls):
+    """What keeps tests/test_gpu_topk_rows.py::test_select_exit_levels from being vacuous, with no GPU: for a
+    byte_row of level L (tests/_util.py), in both directions, the host model of the four-level loop ends at level L
+    for k at every cumulative digit count but the last, runs through all four levels one entry later, and ends at
+    level 0 for k = cols; over the levels that is every exit, 0 to 3, and the run through (4)."""
+    cols = TOPK_ROWS_CLASS_COLS[cls]
+    assert rs.TOPK_ROWS_KERNELS[cls] == ("wave" if cols <= 256 else "small" if cols <= 1024 else
+                                         "lds" if cols <= 16384 else "stream")
+    for m in (np.uint32(0), np.uint32(0xFFFFFFFF)):
+        seen = set()
+        for level in range(4):
+            for seed in (40, 41, 42):
+                x = byte_row(cols, level, seed) ^ m
+                varies = [b for b in range(4) if np.unique((x >> np.uint32(24 - 8 * b)) & np.uint32(255)).size > 1]
+                assert varies == [level] and np.unique(x).size == 16
+                bounds = digit_boundaries(x, level)
+                assert bounds.size == 16 and bounds[-1] == cols and int(np.diff(bounds).min()) >= 2
+                for b in bounds[:-1]:
+                    assert select_exit_level(x, int(b)) == level, (cols, level, seed, int(b))
+                    assert select_exit_level(x, int(b) + 1) == 4, (cols, level, seed, int(b))
+                assert select_exit_level(x, cols) == 0
+                near = int(bounds[np.argmin(np.abs(bounds - cols // 3))])  # the ks of the GPU test
+                seen |= {select_exit_level(x, k) for k in (near, near + 1, cols)}
+        assert seen == {0, 1, 2, 3, 4}, (cols, int(m), seen)
+
+
+def test_select_exit_level_on_plain_rows():
+    """The model itself on rows whose exits are known by hand."""
+    one = np.full(50, 0x01020304, np.uint32)
+    assert all(select_exit_level(one, k) == (0 if k == 50 else 4) for k in (1, 7, 49, 50))
+    x = np.array([0x10000000, 0x20000000, 0x20000001, 0x30000500, 0x30000600, 0x30000601], np.uint32)
+    # k = 1: the top digit 0x10 holds one entry and one is wanted; k = 2: digit 0x20 holds two, one wanted: down to the
+    # last byte, where digit 0 holds exactly the one; k = 3: both of 0x20; k = 4: 0x30 -> byte 2 (5 | 6, 6): digit 5
+    # holds one; k = 5: digit 6 holds two, one wanted -> the last byte: digit 0 holds one; k = 6: all of 0x30
+    assert [select_exit_level(x, k) for k in range(1, 7)] == [0, 3, 0, 2, 3, 0]
