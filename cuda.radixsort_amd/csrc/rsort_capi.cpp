@@ -94,39 +94,12 @@ struct PhaseScope {
     }
 };
 
-int hip_status(hipError_t e) { return e == hipSuccess ? RSORT_OK : RSORT_ERR_HIP; }
-
-// Copies `words` words of a workspace to the host, behind everything enqueued on s, and waits for them.
-int read_words(uint32_t *host, const uint32_t *dev, size_t words, hipStream_t s) {
-    if (hipMemcpyAsync(host, dev, words * 4, hipMemcpyDeviceToHost, s) != hipSuccess) return RSORT_ERR_HIP;
-    return hip_status(hipStreamSynchronize(s));
-}
-
 bool aligned4(const void *p) { return ((uintptr_t)p & 3u) == 0; }
-
-// a key count every entry takes: [0, 2^32)
-bool key_count_ok(int64_t n) { return n >= 0 && n < ((int64_t)1 << 32); }
 
 bool have_device() {
     int count = 0;
     return hipGetDeviceCount(&count) == hipSuccess && count > 0;
 }
-
-// The one bump allocator of the workspace layouts (carve, seg_carve, topk_carve, topk_rows_carve) and of the host
-// entries' staging buffer (Staging): regions in the order they are taken, each a multiple of 256 B long, `off` the
-// bytes taken so far. A null base is sizing: take returns nullptr and only `off` counts. round_base: the regions start
-// at the base's next multiple of 256 (a caller's workspace of any 4-byte alignment).
-struct Bump {
-    char *base;
-    size_t off = 0;
-    explicit Bump(void *p, bool round_base = false)
-        : base(round_base ? (char *)(((uintptr_t)p + 255u) & ~(uintptr_t)255u) : (char *)p) {}
-    uint32_t *take(size_t bytes) {
-        uint32_t *q = base ? (uint32_t *)(base + off) : nullptr;
-        off += align256(bytes);
-        return q;
-    }
-};
 
 // The whole-line scatter kernels can write these outputs: any 4-B-aligned kout (launch_scatter
 // counts positions from its 128-B-aligned base, i.e. every position moves up by the < 32 keys

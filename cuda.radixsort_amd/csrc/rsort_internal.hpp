@@ -1,9 +1,11 @@
 // rsort_internal.hpp -- shared between the HIP kernels (rsort_kernels.hip, rsort_segmented.hip, rsort_topk.hip) and
-// the host driver (rsort_capi.cpp). Not part of the public ABI (include/rsort.h is).
+// the host drivers (rsort_capi.cpp, rsort_multi.cpp). Not part of the public ABI (include/rsort.h is).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+
+#include "rsort.h"
 
 namespace rsort {
 
@@ -470,6 +472,39 @@ hipError_t launch_topk_rows_select(int cls, const TopkRowsArgs &a, uint32_t grid
 hipError_t launch_topk_rows_offsets(uint32_t *off, uint32_t rows, uint32_t k, hipStream_t s);
 // Resident workgroups per CU of a class's select kernel (occupancy query), 0 on error.
 int topk_rows_blocks_per_cu(int cls);
+
+// ------------------------------------------------------------------------------ host helpers
+// (both host drivers, rsort_capi.cpp and rsort_multi.cpp)
+inline int hip_status(hipError_t e) { return e == hipSuccess ? RSORT_OK : RSORT_ERR_HIP; }
+
+// Copies `bytes` bytes (read_words: `words` words) of device memory to the host, behind everything enqueued on s,
+// and waits for them.
+inline int read_bytes(void *host, const void *dev, size_t bytes, hipStream_t s) {
+    if (hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s) != hipSuccess) return RSORT_ERR_HIP;
+    return hip_status(hipStreamSynchronize(s));
+}
+inline int read_words(uint32_t *host, const uint32_t *dev, size_t words, hipStream_t s) {
+    return read_bytes(host, dev, words * 4, s);
+}
+
+// a key count every entry takes: [0, 2^32)
+inline bool key_count_ok(int64_t n) { return n >= 0 && n < ((int64_t)1 << 32); }
+
+// The one bump allocator of the workspace layouts (carve, seg_carve, topk_carve, topk_rows_carve, multi_bytes) and of
+// the host entries' staging buffer (Staging): regions in the order they are taken, each a multiple of 256 B long,
+// `off` the bytes taken so far. A null base is sizing: take returns nullptr and only `off` counts. round_base: the
+// regions start at the base's next multiple of 256 (a caller's workspace of any 4-byte alignment).
+struct Bump {
+    char *base;
+    size_t off = 0;
+    explicit Bump(void *p, bool round_base = false)
+        : base(round_base ? (char *)(((uintptr_t)p + 255u) & ~(uintptr_t)255u) : (char *)p) {}
+    uint32_t *take(size_t bytes) {
+        uint32_t *q = base ? (uint32_t *)(base + off) : nullptr;
+        off += align256(bytes);
+        return q;
+    }
+};
 
 // Raw next-digit tables (every workgroup of a pass sums the whole R x C table for its own starts) cost
 // O(R x C) reads per workgroup, O(R x C^2) per pass: only plans of at most this many chunks (about one

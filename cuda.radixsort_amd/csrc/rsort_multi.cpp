@@ -102,15 +102,15 @@ struct MultiTimer {
     }
 };
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // step 1's all-gathered words per rank: key count, values flags, local status
-constexpr size_t kNWords = 3;
+constexpr size_t kNWords = 3, kNStatusWord = 2;
+// step 4's: the bucket counts in [0, buckets), then the capacity and the local status at fixed words
+constexpr size_t kRowWords = kMaxBuckets + 2, kCapWord = kMaxBuckets, kStatusWord = kMaxBuckets + 1;
 
 struct MultiCarve {
     uint32_t *part_k, *part_v;
     uint64_t *n_send, *n_all;      // [kNWords], [world][kNWords]
-    uint64_t *c_send, *c_all;      // [kMaxBuckets + 2], [world][kMaxBuckets + 2]: counts, capacity, status
+    uint64_t *c_send, *c_all;      // [kRowWords], [world][kRowWords]: counts, capacity, status
     uint32_t *starts;              // [kMaxBuckets + 1]
     uint32_t *samp_send, *samp_all;  // [kSampleBudget + 1], [world][...]: the sample row + the status
     size_t control_bytes;          // the buffers above part_k
@@ -118,10 +118,7 @@ struct MultiCarve {
     size_t sub_bytes;
 };
 
-int64_t samples_per_rank(int world) { return std::max<int64_t>(1, kSampleBudget / world); }
-
 size_t sub_bytes(int64_t n, int64_t cap, int k, int pairs, int world) {
-    (void)world;
     size_t a = rsort_partition_workspace_size(n, kMaxSplitters + 1, pairs);  // (any bucket count: overlap mode)
     // the gathered sample: world rows of at most kSampleBudget samples
     size_t b = rsort_workspace_size(world * kSampleBudget, 8, 0) + ((size_t)4 << 8 << 12);
@@ -133,33 +130,27 @@ size_t sub_bytes(int64_t n, int64_t cap, int k, int pairs, int world) {
     return std::max(a, std::max(b, c));
 }
 
+// The layout: one Bump walk (rsort_internal.hpp), like the sort's carve; returns its bytes. base == nullptr: sizing.
 size_t multi_bytes(int64_t n, int64_t cap, int k, int pairs, int world, MultiCarve *mc, void *base) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += al256(bytes);
-        return (char *)base + o;
-    };
+    Bump b(base);
     MultiCarve m{};
     // the collectives' small buffers first: a rank whose workspace is too small for the rest still
     // takes part in them (with its error status, so every rank returns it together)
-    m.n_send = (uint64_t *)take(kNWords * 8);
-    m.n_all = (uint64_t *)take((size_t)kMaxRanks * kNWords * 8);
-    m.c_send = (uint64_t *)take((size_t)(kMaxBuckets + 2) * 8);
-    m.c_all = (uint64_t *)take((size_t)kMaxRanks * (kMaxBuckets + 2) * 8);
-    m.starts = (uint32_t *)take((size_t)(kMaxBuckets + 1) * 4);
-    m.samp_send = (uint32_t *)take((size_t)(kSampleBudget + 1) * 4);
-    m.samp_all = (uint32_t *)take((size_t)world * (kSampleBudget + 1) * 4);
-    m.control_bytes = off;
-    m.part_k = (uint32_t *)take((size_t)n * 4);
-    m.part_v = pairs ? (uint32_t *)take((size_t)n * 4) : nullptr;
+    m.n_send = (uint64_t *)b.take(kNWords * 8);
+    m.n_all = (uint64_t *)b.take((size_t)kMaxRanks * kNWords * 8);
+    m.c_send = (uint64_t *)b.take(kRowWords * 8);
+    m.c_all = (uint64_t *)b.take((size_t)kMaxRanks * kRowWords * 8);
+    m.starts = b.take((size_t)(kMaxBuckets + 1) * 4);
+    m.samp_send = b.take((size_t)(kSampleBudget + 1) * 4);
+    m.samp_all = b.take((size_t)world * (kSampleBudget + 1) * 4);
+    m.control_bytes = b.off;
+    m.part_k = b.take((size_t)n * 4);
+    m.part_v = pairs ? b.take((size_t)n * 4) : nullptr;
     m.sub_bytes = sub_bytes(n, cap, k, pairs, world);
-    m.sub = take(m.sub_bytes);
+    m.sub = b.take(m.sub_bytes);
     if (mc) *mc = m;
-    return off;
+    return b.off;
 }
-
-int hip_st(hipError_t e) { return e == hipSuccess ? RSORT_OK : RSORT_ERR_HIP; }
 
 // A second stream per device (with its two events) for work that overlaps the exchange: created on
 // first use, kept for the process. Concurrent multi-GPU sorts on one device (the loopback tests'
@@ -194,11 +185,39 @@ SideStream *side_stream() {
     return x;
 }
 
-void side_release(SideStream *x) {
-    if (!x) return;
-    std::lock_guard<std::mutex> g(g_side_mu);
-    x->busy = false;
-}
+// One sort's use of a side stream beside its own stream `s`, and the only place that touches the two events. Its rule:
+// on EVERY way out of the scope while the side stream holds work (an own-range copy, the lower half's sort) `s` first
+// waits for it, so a caller that synchronises `s` after an error never frees buffers a side-stream kernel still
+// writes; only then does the stream go back to the pool (a later user enqueues behind the work anyway).
+struct SideScope {
+    SideStream *x;
+    hipStream_t s;
+    bool pending = false;  // the side stream holds work `s` must wait for
+    explicit SideScope(hipStream_t stream) : x(side_stream()), s(stream) {}
+    ~SideScope() {
+        (void)join();
+        std::lock_guard<std::mutex> g(g_side_mu);
+        if (x) x->busy = false;
+    }
+    // where work that may run beside `s` goes: the side stream, behind everything enqueued on `s` so far -- or `s`
+    // itself when there is no side stream or it still holds work; mark() after enqueueing on the side stream
+    hipStream_t fork() {
+        const bool forked = x && !pending && hipEventRecord(x->ready, s) == hipSuccess &&
+                            hipStreamWaitEvent(x->s, x->ready, 0) == hipSuccess;
+        return forked ? x->s : s;
+    }
+    int mark() {
+        if (hipEventRecord(x->done, x->s) != hipSuccess) return RSORT_ERR_HIP;
+        pending = true;
+        return RSORT_OK;
+    }
+    // `s` waits for the side stream's work (a failed wait leaves it pending: the destructor tries again)
+    int join() {
+        if (pending && hipStreamWaitEvent(s, x->done, 0) != hipSuccess) return RSORT_ERR_HIP;
+        pending = false;
+        return RSORT_OK;
+    }
+};
 
 // ------------------------------------------------------------------------------ RCCL transport
 // Every RCCL step is bounded: RCCL itself never times out, so a peer that died or
@@ -421,7 +440,7 @@ int host_allgather(void *ctx, const void *d_send, void *d_recv, size_t bytes, vo
     if (st) return st;
     if (bytes && hipMemcpyAsync(d_recv, c->recv.data(), world * bytes, hipMemcpyHostToDevice, s) != hipSuccess)
         return RSORT_ERR_HIP;
-    return hip_st(hipStreamSynchronize(s));
+    return hip_status(hipStreamSynchronize(s));
 }
 
 int host_exchange(void *ctx, void *const *d_send, const size_t *send_bytes, void *const *d_recv,
@@ -449,327 +468,335 @@ int host_exchange(void *ctx, void *const *d_send, const size_t *send_bytes, void
     for (int p = 0; p < world; ++p)
         if (recv_bytes[p] && hipMemcpyAsync(d_recv[p], hr[p], recv_bytes[p], hipMemcpyHostToDevice, s) != hipSuccess)
             return RSORT_ERR_HIP;
-    return hip_st(hipStreamSynchronize(s));
+    return hip_status(hipStreamSynchronize(s));
 }
 
 // ------------------------------------------------------------------------------ the sort
-int d2h(void *h, const void *d, size_t bytes, hipStream_t s) {
-    if (hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s) != hipSuccess) return RSORT_ERR_HIP;
-    return hip_st(hipStreamSynchronize(s));
+// One call's state: the caller's arguments and what the steps below share.
+struct MultiCall {
+    const uint32_t *keys, *vals;
+    int64_t n;  // (0 once the rank has failed its checks: nothing reads the keys of a failed rank)
+    uint32_t *keys_out, *vals_out;
+    int64_t capacity, *out_n, *out_offset;
+    int k_bits, world, me, pairs;
+    const rsort_transport *tr;
+    hipStream_t s;
+    MultiTimer timer;
+    // halves per rank, and virtual ranks: world * H (the planning functions run for V ranks; multi_sort)
+    int H = 1, V = 1;
+    MultiCarve m{};
+    // The running local status: every local failure but a missing transport or control buffer is carried to the
+    // peers in the next all-gather (a status word per rank) and returned by every rank together -- the lowest rank's
+    // first -- instead of leaving the peers waiting in a collective this rank never joins (a rank that dies instead
+    // is caught by the RCCL transport's bounded waits: rccl_finish).
+    int local = RSORT_OK;
+    rsort_multi_stats stats{};
+};
+
+// One status-carrying all-gather of rows of `row` words. The last `up` words of this rank's row come from `host`
+// (the whole row, or only the status word of a row the device filled); every rank's row is read back into `all`
+// -- all == nullptr: only its status word, the one at `at` -- and the lowest rank's non-zero status is returned.
+template <class W>
+int gather_status(MultiCall &c, const W *host, size_t up, W *d_send, W *d_all, size_t row, size_t at, W *all) {
+    if (hipMemcpyAsync(d_send + (row - up), host, up * sizeof(W), hipMemcpyHostToDevice, c.s) != hipSuccess)
+        return RSORT_ERR_HIP;
+    int st;
+    if ((st = c.tr->allgather(c.tr->ctx, d_send, d_all, row * sizeof(W), c.s))) return st;
+    W status[kMaxRanks];
+    if (all) {
+        if ((st = read_bytes(all, d_all, (size_t)c.world * row * sizeof(W), c.s))) return st;
+        for (int r = 0; r < c.world; ++r) status[r] = all[r * row + at];
+    } else {
+        for (int r = 0; r < c.world; ++r)
+            if (hip_status(hipMemcpyAsync(&status[r], d_all + r * row + at, sizeof(W), hipMemcpyDeviceToHost, c.s)))
+                return RSORT_ERR_HIP;
+        if (hipStreamSynchronize(c.s) != hipSuccess) return RSORT_ERR_HIP;
+    }
+    for (int r = 0; r < c.world; ++r)
+        if (status[r] != 0) return (int)status[r];
+    return RSORT_OK;
+}
+
+// The argument checks past the transport's. A workspace without room for the control buffers is returned at once (the
+// rank cannot even tell its peers it failed); everything else becomes the local status.
+int check_args(MultiCall &c, void *ws, size_t workspace_bytes) {
+    const bool sizes_ok = key_count_ok(c.n) && key_count_ok(c.capacity);
+    const int64_t n = sizes_ok ? c.n : 0, cap = sizes_ok ? c.capacity : 0;
+    const size_t need = multi_bytes(n, cap, c.k_bits, c.pairs, c.world, &c.m, ws);
+    if (workspace_bytes < c.m.control_bytes) return RSORT_ERR_WORKSPACE;
+    if (c.k_bits < kMinBits || c.k_bits > kMaxBits) c.local = RSORT_ERR_BITS;
+    else if (!sizes_ok) c.local = RSORT_ERR_SIZE;
+    else if (!c.out_n || !c.out_offset || (c.n > 0 && !c.keys) || (c.capacity > 0 && !c.keys_out))
+        c.local = RSORT_ERR_ARG;
+    else if (workspace_bytes < need) c.local = RSORT_ERR_WORKSPACE;
+    if (c.local != RSORT_OK) c.n = 0;
+    return RSORT_OK;
+}
+
+// One rank without RSORT_MULTI_FULL: the partition would be one bucket (a copy) and the exchange a self copy, so the
+// keys go straight through the local sort (same output, no peers to agree with).
+int sort_direct(MultiCall &c) {
+    if (c.local != RSORT_OK) return c.local;
+    if (c.n > c.capacity) return RSORT_ERR_CAPACITY;
+    c.timer.mark(MultiTimer::kExchange);  // (nothing exchanged: the whole time is the local sort)
+    int st;
+    rsort_plan p;
+    // (the multi-GPU path's local sorts never take the hybrid route: said here, not left to its gate)
+    if (c.n > 0 && ((st = rsort_plan_make(c.n, c.k_bits, c.pairs, 0, &p)) ||
+                    (st = rsort_sort_planned_ex(&p, c.keys, c.vals, c.keys_out, c.vals_out, c.m.sub, c.m.sub_bytes, c.s,
+                                                RSORT_SORT_NO_HYBRID))))
+        return st;
+    *c.out_n = c.n;
+    *c.out_offset = 0;
+    c.stats.direct = c.stats.halves = 1;
+    c.stats.n_out = c.stats.send_keys[0] = c.stats.recv_keys[0] = c.n;
+    return c.timer.finish(c.stats);
+}
+
+// 1. key counts, value flags and statuses -> the sampling plan. A rank sorts pairs when it passes values or a values
+//    output (one with no keys may pass an empty, NULL values input); a mismatch between the ranks is an argument
+//    error on every rank (all see the same flags).
+int gather_counts(MultiCall &c, rsort_sample_plan *sp) {
+    const uint64_t mine[kNWords] = {(uint64_t)c.n, (uint64_t)(c.pairs | (c.vals ? 2 : 0) | (c.vals_out ? 4 : 0)),
+                                    (uint64_t)c.local};
+    uint64_t nf[kNWords * kMaxRanks];
+    int st;
+    if ((st = gather_status(c, mine, kNWords, c.m.n_send, c.m.n_all, kNWords, kNStatusWord, nf))) return st;
+    int64_t n_all[kMaxRanks] = {0};  // per virtual rank: rank r's keys at r * H, none at the others
+    bool any_pairs = false, bad = false;
+    for (int r = 0; r < c.world; ++r) {
+        n_all[r * c.H] = (int64_t)nf[kNWords * r];
+        any_pairs |= (nf[kNWords * r + 1] & 1) != 0;
+    }
+    for (int r = 0; r < c.world && any_pairs; ++r)
+        bad |= !(nf[kNWords * r + 1] & 4) || ((int64_t)nf[kNWords * r] > 0 && !(nf[kNWords * r + 1] & 2));
+    if (bad) return RSORT_ERR_ARG;
+    if ((st = rsort_multi_sample_plan(c.V, n_all, std::max<int64_t>(1, kSampleBudget / c.V), sp))) return st;
+    return sp->row_len > kSampleBudget ? RSORT_ERR_ARG : RSORT_OK;  // (cannot happen: budget / V per virtual rank)
+}
+
+// 2. sample (+ this rank's status in the row's last word), gather, sort on the device, read the V - 1 quantile keys
+//    and whether each is hot. A failure after the gather stays in c.local (plan_splitters).
+int sample_quantiles(MultiCall &c, const rsort_sample_plan &sp, uint32_t *q, int *hot) {
+    const MultiCarve &m = c.m;
+    const size_t row = (size_t)sp.row_len + 1;
+    if (launch_sample(c.keys, (uint64_t)c.n, (uint64_t)sp.stride, (uint64_t)sp.count[c.me * c.H], (uint64_t)sp.row_len,
+                      m.samp_send, c.s) != hipSuccess)
+        c.local = RSORT_ERR_HIP;
+    const uint32_t lst = (uint32_t)c.local;
+    int st;
+    if ((st = gather_status<uint32_t>(c, &lst, 1, m.samp_send, m.samp_all, row, row - 1, nullptr))) return st;
+    if (c.V == 1 || sp.total <= 0) return RSORT_OK;
+    // the rows (each followed by its status word) sorted as one array: the status words are 0 and sort first, so
+    // the quantile positions move up by world (and the rows' padding, 0xFFFFFFFF, sorts after the sp.total samples)
+    const int64_t ns = (int64_t)c.world * (int64_t)row;
+    profile_pause(1);  // (its passes are part of the plan phase, not the measured local sort)
+    c.local = rsort_u32_device(m.samp_all, m.samp_all, ns, 8, m.sub, m.sub_bytes, c.s);
+    profile_pause(-1);
+    // each quantile key and the samples hot_reach away on both sides: the key is hot (its own equal-keys bucket,
+    // rsort_multi_splitters_make_hot) when either is the same key
+    const int64_t L = std::max<int64_t>(1, sp.total / ((int64_t)c.V * 128));
+    uint32_t nb[kMaxRanks][2];
+    for (int i = 1; i < c.V && !c.local; ++i) {
+        const int64_t qi = rsort_multi_quantile_index(&sp, i);
+        const int64_t at[3] = {qi, qi - L, qi + L};
+        uint32_t *dst[3] = {&q[i - 1], &nb[i - 1][0], &nb[i - 1][1]};
+        nb[i - 1][0] = nb[i - 1][1] = 0;
+        for (int j = 0; j < 3 && !c.local; ++j) {
+            if (at[j] < 0 || at[j] >= sp.total) continue;  // (a neighbour outside the samples: not hot there)
+            if (hipMemcpyAsync(dst[j], m.samp_all + c.world + at[j], 4, hipMemcpyDeviceToHost, c.s) != hipSuccess)
+                c.local = RSORT_ERR_HIP;
+        }
+    }
+    if (!c.local && hipStreamSynchronize(c.s) != hipSuccess) c.local = RSORT_ERR_HIP;
+    for (int i = 1; i < c.V && !c.local; ++i) {
+        const int64_t qi = rsort_multi_quantile_index(&sp, i);
+        hot[i - 1] = (qi - L >= 0 && nb[i - 1][0] == q[i - 1]) || (qi + L < sp.total && nb[i - 1][1] == q[i - 1]);
+    }
+    if (!c.local) c.local = injected(c.me, 1);
+    return RSORT_OK;
+}
+
+// 3. the splitters. A rank that failed since the last status exchange (the sample sort, a quantile copy) still joins
+//    the next all-gather with a row of its peers' size and its status in it: it plans on placeholder quantiles (all 0,
+//    monotone) instead of its partial ones, and a failure of the pure planning is carried the same way, not returned.
+void plan_splitters(MultiCall &c, uint32_t *q, int *hot, rsort_multi_splitters *spl) {
+    if (c.local) {
+        memset(q, 0, kMaxRanks * sizeof(*q));
+        memset(hot, 0, kMaxRanks * sizeof(*hot));
+    }
+    const int st = rsort_multi_splitters_make_hot(c.V, q, hot, spl);  // pure, identical on every healthy rank
+    if (st) {
+        if (!c.local) c.local = st;
+        memset(spl, 0, sizeof(*spl));
+        spl->world = c.V;
+    }
+    c.timer.mark(MultiTimer::kPlan);
+}
+
+// 3-4. stable partition into the splitters' buckets; then count matrix + capacities + statuses -> every virtual rank's
+//      exchange plan, xv[V] (the same on every rank: a capacity error comes back from all of them before any key moves)
+int partition_and_plan(MultiCall &c, const rsort_multi_splitters &spl, rsort_exchange_plan *xv) {
+    const MultiCarve &m = c.m;
+    const int world = c.world, H = c.H, buckets = std::min(spl.nsplit + 1, kMaxSplitters + 1);
+    int &local = c.local;
+    if (spl.nsplit + 1 > kMaxSplitters + 1 && !local) local = RSORT_ERR_ARG;  // (pure: every rank alike)
+    uint32_t starts[kMaxBuckets + 1] = {0};
+    if (!local) local = injected(c.me, 2);
+    if (!local)
+        local = rsort_partition_device(c.keys, c.vals, m.part_k, m.part_v, c.n, spl.split, buckets, m.starts, m.sub,
+                                       m.sub_bytes, c.s);
+    if (!local) local = read_words(starts, m.starts, (size_t)(buckets + 1), c.s);
+    if (!local) {  // the partition's self-check (its scatter's rank check): a failure stops every rank below
+        int pf = 0;
+        local = rsort_partition_check(c.n, buckets, c.vals != nullptr ? 1 : 0, m.sub, &pf, c.s);
+        if (!local && pf) local = RSORT_ERR_CHECK;
+    }
+    // (a row of fixed size whatever this rank's bucket count -- a failed rank's may differ: the all-gather matches)
+    uint64_t rowc[kRowWords] = {0}, all[kMaxRanks * kRowWords];
+    for (int b = 0; b < buckets && !local; ++b) rowc[b] = (uint64_t)(starts[b + 1] - starts[b]);
+    rowc[kCapWord] = (uint64_t)c.capacity;
+    rowc[kStatusWord] = (uint64_t)local;
+    int st;
+    if ((st = gather_status(c, rowc, kRowWords, m.c_send, m.c_all, kRowWords, kStatusWord, all))) return st;
+    int64_t counts[kMaxRanks * kMaxBuckets] = {0}, caps[kMaxRanks], cap_of[kMaxRanks];
+    for (int r = 0; r < world; ++r) {
+        for (int b = 0; b < buckets; ++b) counts[r * H * buckets + b] = (int64_t)all[r * kRowWords + b];
+        cap_of[r] = (int64_t)all[r * kRowWords + kCapWord];
+        for (int h = 0; h < H; ++h) caps[r * H + h] = cap_of[r];  // (the halves' sum is checked below)
+    }
+    for (int v = 0; v < c.V; ++v) {
+        st = rsort_multi_exchange_plan(c.V, v, buckets, counts, &spl, caps, &xv[v]);
+        if (st != RSORT_OK && st != RSORT_ERR_CAPACITY) return st;
+    }
+    for (int r = 0; r < world; ++r) {  // the capacity check is on each rank's total
+        int64_t tot = 0;
+        for (int h = 0; h < H; ++h) tot += xv[r * H + h].n_recv;
+        if (tot > cap_of[r]) return RSORT_ERR_CAPACITY;
+    }
+    return RSORT_OK;
+}
+
+// 5. half h's exchange into ok / ov: the own range by a device copy beside the messages (on the side stream where it
+//    is free), every other message through the transport on `s`, in equal rounds of <= the piece limit
+int exchange_half(MultiCall &c, SideScope &side, const rsort_exchange_plan &xs, const rsort_exchange_plan &xd, int h,
+                  uint32_t *ok, uint32_t *ov, int64_t rounds, int64_t piece) {
+    const MultiCarve &m = c.m;
+    const int me = c.me, H = c.H, own_dst = me * H + h, own_src = me * H;
+    if (xs.send_cnt[own_dst] != xd.recv_cnt[own_src]) return RSORT_ERR_ARG;
+    int st;
+    const int64_t own = xs.send_cnt[own_dst], from = xs.send_off[own_dst], to = xd.recv_off[own_src];
+    if (own > 0) {
+        const hipStream_t cs = side.fork();
+        for (int arr = 0; arr < (c.pairs ? 2 : 1); ++arr)
+            if (hipMemcpyAsync((arr ? ov : ok) + to, (arr ? m.part_v : m.part_k) + from, (size_t)own * 4,
+                               hipMemcpyDeviceToDevice, cs) != hipSuccess)
+                return RSORT_ERR_HIP;
+        if (cs != c.s && (st = side.mark())) return st;
+    }
+    for (int64_t rd = 0; rd < rounds; ++rd) {
+        for (int arr = 0; arr < (c.pairs ? 2 : 1); ++arr) {
+            uint32_t *src = arr ? m.part_v : m.part_k, *dst = arr ? ov : ok;
+            void *sp[kMaxRanks], *rp[kMaxRanks];
+            size_t sb[kMaxRanks], rb[kMaxRanks];
+            for (int p = 0; p < c.world; ++p) {
+                const int dv = p * H + h, sv = p * H;  // virtual destination / source
+                const int64_t a0 = std::min(xs.send_cnt[dv], rd * piece), a1 = std::min(xs.send_cnt[dv], (rd + 1) * piece);
+                const int64_t b0 = std::min(xd.recv_cnt[sv], rd * piece), b1 = std::min(xd.recv_cnt[sv], (rd + 1) * piece);
+                sp[p] = src + xs.send_off[dv] + a0;
+                rp[p] = dst + xd.recv_off[sv] + b0;
+                sb[p] = p == me ? 0 : (size_t)(a1 - a0) * 4;
+                rb[p] = p == me ? 0 : (size_t)(b1 - b0) * 4;
+            }
+            if ((st = c.tr->exchange(c.tr->ctx, sp, sb, rp, rb, c.s))) return st;
+        }
+    }
+    return RSORT_OK;
+}
+
+// 6. local sort of the n keys that arrived in ok / ov, in place; beside: on the side stream, while the next half is
+//    exchanged on `s` (the side stream then holds work, so that half's own copy stays on `s`)
+int sort_half(MultiCall &c, SideScope &side, int64_t n, uint32_t *ok, uint32_t *ov, bool beside) {
+    if (n <= 0) return RSORT_OK;
+    int st;
+    rsort_plan p;
+    if ((st = rsort_plan_make(n, c.k_bits, c.pairs, 0, &p))) return st;
+    const hipStream_t ss = beside ? side.fork() : c.s;
+    // (a rank's keys cover 1 / N of the key space: their (digit 3, digit 2) buckets would overflow)
+    if ((st = rsort_sort_planned_ex(&p, ok, ov, ok, ov, c.m.sub, c.m.sub_bytes, ss, RSORT_SORT_NO_HYBRID))) return st;
+    return ss != c.s ? side.mark() : RSORT_OK;
+}
+
+// 5-6. per half: the exchange, then the local sort of what arrived (the first half's beside the second's exchange)
+int exchange_and_sort(MultiCall &c, const rsort_exchange_plan *xv) {
+    const int me = c.me, H = c.H;
+    const rsort_exchange_plan &xs = xv[me * H];  // (this rank sends as virtual rank me * H, receives as me * H + h)
+    int st;
+    int64_t rounds = 0, piece = 0;
+    if ((st = rsort_multi_exchange_rounds(xs.max_message, g_piece.load(), &rounds, &piece))) return st;
+    c.timer.mark(MultiTimer::kPartition);
+    c.stats.halves = H;
+    c.stats.rounds = rounds;
+    for (int p = 0; p < c.world; ++p)
+        for (int h = 0; h < H; ++h) {
+            c.stats.send_keys[p] += xs.send_cnt[p * H + h];
+            c.stats.recv_keys[p] += xv[me * H + h].recv_cnt[p * H];
+        }
+    SideScope side(c.s);  // (every return below leaves through its destructor)
+    int64_t base = 0;
+    for (int h = 0; h < H; ++h) {
+        const rsort_exchange_plan &xd = xv[me * H + h];
+        const bool last = h + 1 == H;
+        uint32_t *ok = c.keys_out + base, *ov = c.pairs ? c.vals_out + base : nullptr;
+        if ((st = exchange_half(c, side, xs, xd, h, ok, ov, rounds, piece))) return st;
+        // this half has arrived (on `s`, and its own range on the side stream); under the overlap the exchange
+        // phase ends with the last message, before waiting for the lower half's sort
+        if (last && H > 1) c.timer.mark(MultiTimer::kExchange);
+        if ((st = side.join())) return st;
+        if (last && H == 1) c.timer.mark(MultiTimer::kExchange);
+        if ((st = sort_half(c, side, xd.n_recv, ok, ov, !last))) return st;
+        base += xd.n_recv;
+    }
+    if ((st = side.join())) return st;
+    *c.out_n = c.stats.n_out = base;
+    *c.out_offset = xs.offset;
+    return c.timer.finish(c.stats);
 }
 
 int multi_sort(const uint32_t *d_keys, const uint32_t *d_vals, int64_t n, uint32_t *d_keys_out, uint32_t *d_vals_out,
                int64_t capacity, int64_t *out_n, int64_t *out_offset, int k_bits, const rsort_transport *tr,
                void *d_workspace, size_t workspace_bytes, hipStream_t s) {
-    // What every collective needs: a transport, this rank's place in it and the small control
-    // buffers. Without them a rank cannot even tell its peers it failed (caller error).
+    // (without a transport, its place in it and the control buffers a rank cannot even tell its peers it failed)
     if (!tr || !tr->allgather || !tr->exchange || !d_workspace) return RSORT_ERR_ARG;
-    const int world = tr->world, me = tr->rank;
+    const int world = tr->world, me = tr->rank, opts = g_multi_opts.load();
     if (world < 1 || world > kMaxRanks || me < 0 || me >= world) return RSORT_ERR_ARG;
-    const bool sizes_ok = n >= 0 && n < ((int64_t)1 << 32) && capacity >= 0 && capacity < ((int64_t)1 << 32);
-    // a rank sorts pairs when it passes values or a values output (a rank with no keys may pass
-    // an empty, NULL values input); the ranks agree on it in step 1
-    const int pairs = (d_vals != nullptr || d_vals_out != nullptr) ? 1 : 0;
-    MultiCarve m;
-    const size_t need = multi_bytes(sizes_ok ? n : 0, sizes_ok ? capacity : 0, k_bits, pairs, world, &m, d_workspace);
-    if (workspace_bytes < m.control_bytes) return RSORT_ERR_WORKSPACE;
-    // Every other local failure is carried to the peers in the next all-gather (a status word per
-    // rank) and returned by every rank together -- the lowest rank's status first -- instead of
-    // leaving the peers waiting in a collective this rank never joins (a rank that dies instead is
-    // caught by the RCCL transport's bounded waits: rccl_finish).
-    int local = RSORT_OK;
-    if (k_bits < kMinBits || k_bits > kMaxBits) local = RSORT_ERR_BITS;
-    else if (!sizes_ok) local = RSORT_ERR_SIZE;
-    else if (!out_n || !out_offset || (n > 0 && !d_keys) || (capacity > 0 && !d_keys_out)) local = RSORT_ERR_ARG;
-    else if (workspace_bytes < need) local = RSORT_ERR_WORKSPACE;
-    if (local != RSORT_OK) n = 0;  // (nothing below reads the keys of a failed rank)
+    const int pairs = (d_vals != nullptr || d_vals_out != nullptr) ? 1 : 0;  // (the ranks agree on it in step 1)
+    MultiCall c{d_keys, d_vals, n, d_keys_out, d_vals_out, capacity, out_n, out_offset, k_bits, world, me, pairs,
+                tr, s, MultiTimer(g_multi_prof.load() != 0, s)};
     int st;
-    const int opts = g_multi_opts.load();
-    rsort_multi_stats stats;
-    memset(&stats, 0, sizeof(stats));
-    stats.world = world;
-    stats.rank = me;
-    stats.n_in = n;
-    stats.bytes_per_key = pairs ? 8 : 4;
-    MultiTimer timer(g_multi_prof.load() != 0, s);
-    timer.mark(MultiTimer::kStart);
-    if (world == 1 && !(opts & RSORT_MULTI_FULL)) {
-        // one rank: the partition would be one bucket (a copy) and the exchange a self copy, so the
-        // keys go straight through the local sort (same output, no peers to agree with)
-        if (local != RSORT_OK) return local;
-        if (n > capacity) return RSORT_ERR_CAPACITY;
-        timer.mark(MultiTimer::kExchange);  // (nothing exchanged: the whole time is the local sort)
-        if (n > 0) {
-            rsort_plan p;
-            if ((st = rsort_plan_make(n, k_bits, pairs, 0, &p))) return st;
-            // (the multi-GPU path's local sorts never take the hybrid route: said here, not left to its gate)
-            if ((st = rsort_sort_planned_ex(&p, d_keys, d_vals, d_keys_out, d_vals_out, m.sub, m.sub_bytes, s,
-                                            RSORT_SORT_NO_HYBRID)))
-                return st;
-        }
-        *out_n = n;
-        *out_offset = 0;
-        stats.direct = 1;
-        stats.halves = 1;
-        stats.n_out = n;
-        stats.send_keys[0] = stats.recv_keys[0] = n;
-        return timer.finish(stats);
-    }
-    // RSORT_MULTI_OVERLAP: every rank's key range is cut in two (H = 2 virtual ranks per rank, the
-    // planning functions run for world * H ranks); the lower half is exchanged first and sorted on a
-    // side stream while the upper half is exchanged
-    // (automatic: 2 <= world <= RSORT_MULTI_AUTO_OVERLAP_MAX_WORLD, rsort.h and DESIGN §5)
+    if ((st = check_args(c, d_workspace, workspace_bytes))) return st;
+    c.stats.world = world;
+    c.stats.rank = me;
+    c.stats.n_in = c.n;
+    c.stats.bytes_per_key = pairs ? 8 : 4;
+    c.timer.mark(MultiTimer::kStart);
+    if (world == 1 && !(opts & RSORT_MULTI_FULL)) return sort_direct(c);
+    // RSORT_MULTI_OVERLAP (automatic: 2 <= world <= RSORT_MULTI_AUTO_OVERLAP_MAX_WORLD, rsort.h and DESIGN §5): every
+    // rank's key range is cut in two; the lower half is exchanged first and sorted while the upper half is exchanged
     const bool ov = (opts & RSORT_MULTI_OVERLAP) != 0 ||
                     (!(opts & RSORT_MULTI_NO_OVERLAP) && world <= RSORT_MULTI_AUTO_OVERLAP_MAX_WORLD);
-    const int H = (ov && world >= 2 && 2 * world <= kMaxRanks) ? 2 : 1;
-    const int V = world * H;
-    auto first_status = [&](const uint64_t *words, size_t stride, size_t at) {
-        for (int r = 0; r < world; ++r)
-            if (words[(size_t)r * stride + at] != 0) return (int)words[(size_t)r * stride + at];
-        return (int)RSORT_OK;
-    };
-
-    // 1. key counts, value flags and statuses -> sampling plan; a values mismatch between ranks is
-    //    an argument error on every rank (all see the same flags)
-    const uint64_t mine[kNWords] = {(uint64_t)n, (uint64_t)(pairs | (d_vals ? 2 : 0) | (d_vals_out ? 4 : 0)),
-                                    (uint64_t)local};
-    if (hipMemcpyAsync(m.n_send, mine, sizeof(mine), hipMemcpyHostToDevice, s) != hipSuccess) return RSORT_ERR_HIP;
-    if ((st = tr->allgather(tr->ctx, m.n_send, m.n_all, sizeof(mine), s))) return st;
-    uint64_t nf[kNWords * kMaxRanks];
-    if ((st = d2h(nf, m.n_all, (size_t)world * sizeof(mine), s))) return st;
-    if ((st = first_status(nf, kNWords, 2))) return st;
-    int64_t n_all[kMaxRanks] = {0};  // per virtual rank: rank r's keys at r * H, none at the others
-    bool any_pairs = false, bad = false;
-    for (int r = 0; r < world; ++r) {
-        n_all[r * H] = (int64_t)nf[kNWords * r];
-        any_pairs |= (nf[kNWords * r + 1] & 1) != 0;
-    }
-    for (int r = 0; r < world && any_pairs; ++r)
-        bad |= !(nf[kNWords * r + 1] & 4) || ((int64_t)nf[kNWords * r] > 0 && !(nf[kNWords * r + 1] & 2));
-    if (bad) return RSORT_ERR_ARG;
+    c.H = (ov && world >= 2 && 2 * world <= kMaxRanks) ? 2 : 1;
+    c.V = world * c.H;
     rsort_sample_plan sp;
-    if ((st = rsort_multi_sample_plan(V, n_all, samples_per_rank(V), &sp))) return st;
-    if (sp.row_len > kSampleBudget) return RSORT_ERR_ARG;  // cannot happen: budget / V per virtual rank
-
-    // 2. sample (+ this rank's status in the row's last word), gather, sort on the device, read
-    //    the quantile keys
-    const size_t row = (size_t)sp.row_len + 1;
-    if (launch_sample(d_keys, (uint64_t)n, (uint64_t)sp.stride, (uint64_t)sp.count[me * H], (uint64_t)sp.row_len,
-                      m.samp_send, s) != hipSuccess)
-        local = RSORT_ERR_HIP;
-    const uint32_t lst = (uint32_t)local;
-    if (hipMemcpyAsync(m.samp_send + sp.row_len, &lst, 4, hipMemcpyHostToDevice, s) != hipSuccess) return RSORT_ERR_HIP;
-    if ((st = tr->allgather(tr->ctx, m.samp_send, m.samp_all, row * 4, s))) return st;
-    {
-        uint32_t sts[kMaxRanks];
-        for (int r = 0; r < world; ++r)
-            if (hipMemcpyAsync(&sts[r], m.samp_all + (size_t)r * row + sp.row_len, 4, hipMemcpyDeviceToHost, s) !=
-                hipSuccess)
-                return RSORT_ERR_HIP;
-        if (hipStreamSynchronize(s) != hipSuccess) return RSORT_ERR_HIP;
-        for (int r = 0; r < world; ++r)
-            if (sts[r]) return (int)sts[r];
-    }
     uint32_t q[kMaxRanks] = {0};
     int hot[kMaxRanks] = {0};
-    if (V > 1 && sp.total > 0) {
-        // the rows (each followed by its status word) sorted as one array: the status words are 0
-        // and sort first, so the quantile positions move up by world (and the rows' padding, 0xFFFFFFFF,
-        // sorts after the sp.total samples)
-        const int64_t ns = (int64_t)world * (int64_t)row;
-        profile_pause(1);  // (its passes are part of the plan phase, not the measured local sort)
-        local = rsort_u32_device(m.samp_all, m.samp_all, ns, 8, m.sub, m.sub_bytes, s);
-        profile_pause(-1);
-        // each quantile key and the samples hot_reach away on both sides: the key is hot (its own
-        // equal-keys bucket, rsort_multi_splitters_make_hot) when either is the same key
-        const int64_t L = std::max<int64_t>(1, sp.total / ((int64_t)V * 128));
-        uint32_t nb[kMaxRanks][2];
-        for (int i = 1; i < V && !local; ++i) {
-            const int64_t qi = rsort_multi_quantile_index(&sp, i);
-            const int64_t at[3] = {qi, qi - L, qi + L};
-            uint32_t *dst[3] = {&q[i - 1], &nb[i - 1][0], &nb[i - 1][1]};
-            nb[i - 1][0] = nb[i - 1][1] = 0;
-            for (int j = 0; j < 3 && !local; ++j) {
-                if (at[j] < 0 || at[j] >= sp.total) continue;  // (a neighbour outside the samples: not hot there)
-                if (hipMemcpyAsync(dst[j], m.samp_all + world + at[j], 4, hipMemcpyDeviceToHost, s) != hipSuccess)
-                    local = RSORT_ERR_HIP;
-            }
-        }
-        if (!local && hipStreamSynchronize(s) != hipSuccess) local = RSORT_ERR_HIP;
-        for (int i = 1; i < V && !local; ++i) {
-            const int64_t qi = rsort_multi_quantile_index(&sp, i);
-            hot[i - 1] = (qi - L >= 0 && nb[i - 1][0] == q[i - 1]) || (qi + L < sp.total && nb[i - 1][1] == q[i - 1]);
-        }
-        if (!local) local = injected(me, 1);
-        if (local) q[0] = 0xFFFFFFFFu;  // (a failed copy may leave partial quantiles: replaced below)
-    }
-    // From here a rank that failed since the last status exchange (the sample sort, a quantile copy)
-    // still joins the next all-gather with a row of the same size as its peers' and its status in
-    // it: it plans on placeholder quantiles (all 0, monotone) instead of its partial ones, and a
-    // failure of the pure splitter planning is carried the same way instead of returned.
-    if (local) {
-        memset(q, 0, sizeof(q));
-        memset(hot, 0, sizeof(hot));
-    }
     rsort_multi_splitters spl;
-    if ((st = rsort_multi_splitters_make_hot(V, q, hot, &spl))) {  // pure, identical on every healthy rank
-        if (!local) local = st;
-        memset(&spl, 0, sizeof(spl));
-        spl.world = V;
-    }
-    timer.mark(MultiTimer::kPlan);
-
-    // 3. stable partition into the splitters' buckets
-    const int buckets = std::min(spl.nsplit + 1, kMaxSplitters + 1);
-    if (spl.nsplit + 1 > kMaxSplitters + 1 && !local) local = RSORT_ERR_ARG;  // (pure: every rank alike)
-    uint32_t starts[kMaxBuckets + 1] = {0};
-    if (!local) local = injected(me, 2);
-    if (!local)
-        local = rsort_partition_device(d_keys, d_vals, m.part_k, m.part_v, n, spl.split, buckets, m.starts, m.sub,
-                                       m.sub_bytes, s);
-    if (!local) local = d2h(starts, m.starts, (size_t)(buckets + 1) * 4, s);
-    if (!local) {  // the partition's self-check (its scatter's rank check): a failure stops every rank below
-        int pf = 0;
-        local = rsort_partition_check(n, buckets, d_vals != nullptr ? 1 : 0, m.sub, &pf, s);
-        if (!local && pf) local = RSORT_ERR_CHECK;
-    }
-
-    // 4. count matrix + capacities + statuses -> the exchange plans (the same on every rank). The
-    //    row has a fixed size whatever this rank's bucket count (a failed rank's may differ), so the
-    //    all-gather always matches: counts in [0, buckets), capacity and status at fixed words.
-    constexpr int kRow = kMaxBuckets + 2, kCapWord = kMaxBuckets, kStatusWord = kMaxBuckets + 1;
-    uint64_t rowc[kRow] = {0};
-    for (int b = 0; b < buckets && !local; ++b) rowc[b] = (uint64_t)(starts[b + 1] - starts[b]);
-    rowc[kCapWord] = (uint64_t)capacity;
-    rowc[kStatusWord] = (uint64_t)local;
-    const size_t row_bytes = sizeof(rowc);
-    if (hipMemcpyAsync(m.c_send, rowc, row_bytes, hipMemcpyHostToDevice, s) != hipSuccess) return RSORT_ERR_HIP;
-    if ((st = tr->allgather(tr->ctx, m.c_send, m.c_all, row_bytes, s))) return st;
-    uint64_t all[kMaxRanks * kRow];
-    if ((st = d2h(all, m.c_all, (size_t)world * row_bytes, s))) return st;
-    if ((st = first_status(all, (size_t)kRow, (size_t)kStatusWord))) return st;
-    int64_t counts[kMaxRanks * kMaxBuckets] = {0}, caps[kMaxRanks], cap_of[kMaxRanks];
-    for (int r = 0; r < world; ++r) {
-        for (int b = 0; b < buckets; ++b) counts[r * H * buckets + b] = (int64_t)all[r * kRow + b];
-        cap_of[r] = (int64_t)all[r * kRow + kCapWord];
-        for (int h = 0; h < H; ++h) caps[r * H + h] = cap_of[r];  // (the halves' sum is checked below)
-    }
-    // every virtual rank's plan: this rank sends as virtual rank me * H and receives as me * H + h;
-    // the capacity check is on each rank's total
     rsort_exchange_plan xv[kMaxRanks];
-    for (int v = 0; v < V; ++v) {
-        st = rsort_multi_exchange_plan(V, v, buckets, counts, &spl, caps, &xv[v]);
-        if (st != RSORT_OK && st != RSORT_ERR_CAPACITY) return st;
-    }
-    for (int r = 0; r < world; ++r) {
-        int64_t tot = 0;
-        for (int h = 0; h < H; ++h) tot += xv[r * H + h].n_recv;
-        if (tot > cap_of[r]) return RSORT_ERR_CAPACITY;
-    }
-    const rsort_exchange_plan &xs = xv[me * H];  // (all sends of this rank)
-
-    // 5-6. per half: the exchange (the own range by a device copy on a side stream beside the
-    //      messages, which the transport moves on `s`; the rest in equal rounds of <= the piece
-    //      limit), then the local sort of what arrived, in place. With two halves the first half's
-    //      sort runs on the side stream while the second half is exchanged.
-    int64_t rounds = 0, piece = 0;
-    if ((st = rsort_multi_exchange_rounds(xs.max_message, g_piece.load(), &rounds, &piece))) return st;
-    timer.mark(MultiTimer::kPartition);
-    stats.halves = H;
-    stats.rounds = rounds;
-    for (int p = 0; p < world; ++p)
-        for (int h = 0; h < H; ++h) {
-            stats.send_keys[p] += xs.send_cnt[p * H + h];
-            stats.recv_keys[p] += xv[me * H + h].recv_cnt[p * H];
-        }
-    SideStream *side = side_stream();
-    // On EVERY return while the side stream holds work (an own-range copy, the lower half's sort)
-    // `s` first waits for it, so a caller that synchronises `s` after an error never frees buffers
-    // a side-stream kernel still writes; only then does the stream go back to the pool (a later user
-    // enqueues behind the work anyway, and the wait already captured the event's state).
-    struct SideGuard {
-        SideStream *x;
-        hipStream_t s;
-        bool pending = false;  // the side stream holds work `s` must wait for
-        ~SideGuard() {
-            if (x && pending) (void)hipStreamWaitEvent(s, x->done, 0);
-            side_release(x);
-        }
-    } side_guard{side, s};
-    bool &side_pending = side_guard.pending;
-    int64_t base = 0;
-    for (int h = 0; h < H; ++h) {
-        const rsort_exchange_plan &xd = xv[me * H + h];
-        const int own_dst = me * H + h, own_src = me * H;
-        if (xs.send_cnt[own_dst] != xd.recv_cnt[own_src]) return RSORT_ERR_ARG;
-        uint32_t *ok = d_keys_out + base, *ov = pairs ? d_vals_out + base : nullptr;
-        const int64_t own = xs.send_cnt[own_dst];
-        if (own > 0) {
-            hipStream_t cs = s;
-            if (side && !side_pending && hipEventRecord(side->ready, s) == hipSuccess &&
-                hipStreamWaitEvent(side->s, side->ready, 0) == hipSuccess)
-                cs = side->s;
-            if (hipMemcpyAsync(ok + xd.recv_off[own_src], m.part_k + xs.send_off[own_dst], (size_t)own * 4,
-                               hipMemcpyDeviceToDevice, cs) != hipSuccess)
-                return RSORT_ERR_HIP;
-            if (pairs && hipMemcpyAsync(ov + xd.recv_off[own_src], m.part_v + xs.send_off[own_dst], (size_t)own * 4,
-                                        hipMemcpyDeviceToDevice, cs) != hipSuccess)
-                return RSORT_ERR_HIP;
-            if (cs != s) {
-                if (hipEventRecord(side->done, side->s) != hipSuccess) return RSORT_ERR_HIP;
-                side_pending = true;
-            }
-        }
-        for (int64_t rd = 0; rd < rounds; ++rd) {
-            for (int arr = 0; arr < (pairs ? 2 : 1); ++arr) {
-                uint32_t *src = arr ? m.part_v : m.part_k;
-                uint32_t *dst = arr ? ov : ok;
-                void *sp_[kMaxRanks], *rp_[kMaxRanks];
-                size_t sb[kMaxRanks], rb[kMaxRanks];
-                for (int p = 0; p < world; ++p) {
-                    const int dv = p * H + h, sv = p * H;  // virtual destination / source
-                    const int64_t a0 = std::min(xs.send_cnt[dv], rd * piece), a1 = std::min(xs.send_cnt[dv], (rd + 1) * piece);
-                    const int64_t b0 = std::min(xd.recv_cnt[sv], rd * piece), b1 = std::min(xd.recv_cnt[sv], (rd + 1) * piece);
-                    sp_[p] = src + xs.send_off[dv] + a0;
-                    rp_[p] = dst + xd.recv_off[sv] + b0;
-                    sb[p] = p == me ? 0 : (size_t)(a1 - a0) * 4;
-                    rb[p] = p == me ? 0 : (size_t)(b1 - b0) * 4;
-                }
-                if ((st = tr->exchange(tr->ctx, sp_, sb, rp_, rb, s))) return st;
-            }
-        }
-        // this half has arrived (on `s`, and its own range on the side stream); under the overlap the
-        // exchange phase ends with the last message, before waiting for the lower half's sort
-        if (h + 1 == H && H > 1) timer.mark(MultiTimer::kExchange);
-        if (side_pending) {
-            if (hipStreamWaitEvent(s, side->done, 0) != hipSuccess) return RSORT_ERR_HIP;
-            side_pending = false;
-        }
-        if (h + 1 == H && H == 1) timer.mark(MultiTimer::kExchange);
-        if (xd.n_recv > 0) {
-            rsort_plan p;
-            if ((st = rsort_plan_make(xd.n_recv, k_bits, pairs, 0, &p))) return st;
-            hipStream_t ss = s;
-            if (h + 1 < H && side && hipEventRecord(side->ready, s) == hipSuccess &&
-                hipStreamWaitEvent(side->s, side->ready, 0) == hipSuccess)
-                ss = side->s;  // sorted while the next half is exchanged on `s`
-            // (a rank's keys cover 1 / N of the key space: their (digit 3, digit 2) buckets would overflow)
-            if ((st = rsort_sort_planned_ex(&p, ok, ov, ok, ov, m.sub, m.sub_bytes, ss, RSORT_SORT_NO_HYBRID))) return st;
-            if (ss != s) {
-                if (hipEventRecord(side->done, side->s) != hipSuccess) return RSORT_ERR_HIP;
-                side_pending = true;  // (the next half's own copy then stays on `s`)
-            }
-        }
-        base += xd.n_recv;
-    }
-    if (side_pending) {
-        if (hipStreamWaitEvent(s, side->done, 0) != hipSuccess) return RSORT_ERR_HIP;
-        side_pending = false;
-    }
-    *out_n = base;
-    *out_offset = xv[me * H].offset;
-    stats.n_out = base;
-    return timer.finish(stats);
+    if ((st = gather_counts(c, &sp))) return st;               // 1
+    if ((st = sample_quantiles(c, sp, q, hot))) return st;     // 2
+    plan_splitters(c, q, hot, &spl);                           // 3
+    if ((st = partition_and_plan(c, spl, xv))) return st;      // 3-4
+    return exchange_and_sort(c, xv);                           // 5-6
 }
 
 }  // namespace

@@ -659,9 +659,10 @@ def default_capacity(n: int) -> int:
     return int(n + n // 4 + (1 << 16))
 
 
-def multi_sort_device(comm, keys, k_bits=8, vals=None, capacity=None, stream=None, ws=None, out=None):
+def multi_sort_device(comm, keys, k_bits=8, vals=None, capacity=None, stream=None, ws=None, out=None, ws_bytes=None):
     """rsort_u32_multi (comm: RcclComm) or rsort_u32_multi_transport (comm: a Transport):
-    returns (keys_out[:count], vals_out[:count] or None, global offset)."""
+    returns (keys_out[:count], vals_out[:count] or None, global offset). ws_bytes: the workspace_bytes
+    the call is told (tests: less than the workspace holds)."""
     n = keys.numel()
     cap = int(capacity if capacity is not None else default_capacity(n))
     pairs = vals is not None
@@ -672,14 +673,15 @@ def multi_sort_device(comm, keys, k_bits=8, vals=None, capacity=None, stream=Non
     if ws is None or ws.numel() < wsb:
         ws = workspace(wsb, keys.device)
     cnt, off = ctypes.c_int64(), ctypes.c_int64()
+    told = ws.numel() if ws_bytes is None else min(int(ws_bytes), ws.numel())
     if isinstance(comm, Transport):
         st = _lib().rsort_u32_multi_transport(_ptr(keys), _ptr(vals), n, _ptr(kout), _ptr(vout), cap,
                                               ctypes.byref(cnt), ctypes.byref(off), int(k_bits), ctypes.byref(comm),
-                                              _ptr(ws), ws.numel(), _stream(stream))
+                                              _ptr(ws), told, _stream(stream))
         _check(st, "rsort_u32_multi_transport")
     else:
         _check(_lib().rsort_u32_multi(_ptr(keys), _ptr(vals), n, _ptr(kout), _ptr(vout), cap, ctypes.byref(cnt),
-                                      ctypes.byref(off), int(k_bits), comm.handle, _ptr(ws), ws.numel(),
+                                      ctypes.byref(off), int(k_bits), comm.handle, _ptr(ws), told,
                                       _stream(stream)), "rsort_u32_multi")
     c = cnt.value
     return kout[:c], (vout[:c] if pairs else None), off.value

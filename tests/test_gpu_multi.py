@@ -204,11 +204,13 @@ def _loopback_inputs(rank, n, dist_name, pairs):
     return keys, vals
 
 
-def _run_loopback(world, inputs, k, capacity=None, piece=None, opts=0, stats=None, transports=None):
+def _run_loopback(world, inputs, k, capacity=None, piece=None, opts=0, stats=None, transports=None, ws_bytes=None,
+                  timeout=240):
     """world threads in this process, one stream each, calling rsort_u32_multi_transport with
     the loopback transport (or `transports[r]`) on cuda:0 concurrently. Returns per-rank (keys, vals,
-    offset) or the per-rank RSortError statuses. stats: a list that receives every rank's
-    rsort_multi_last_stats (profiling on for the call)."""
+    offset) or the per-rank RSortError statuses. k: one k_bits, or one per rank. stats: a list that receives
+    every rank's rsort_multi_last_stats (profiling on for the call). ws_bytes: per rank, the workspace_bytes it
+    tells the call (None: what its workspace holds). timeout: seconds the ranks' threads are waited for."""
     import threading
     sys.path.insert(0, str(PKG))
     import radixsort as rs
@@ -233,7 +235,9 @@ def _run_loopback(world, inputs, k, capacity=None, piece=None, opts=0, stats=Non
             with torch.cuda.stream(st):
                 kk, vv = dev_in[r]
                 tr = transports[r] if transports is not None else grp.transport(r)
-                ok, ov, off = rs.multi_sort_device(tr, kk, k, vals=vv, capacity=capacity, stream=st)
+                ok, ov, off = rs.multi_sort_device(tr, kk, k[r] if isinstance(k, (list, tuple)) else k, vals=vv,
+                                                   capacity=capacity, stream=st,
+                                                   ws_bytes=ws_bytes[r] if ws_bytes is not None else None)
                 st.synchronize()
                 res[r] = (rs.to_numpy_u32(ok), rs.to_numpy_u32(ov) if ov is not None else None, off)
                 if stats is not None:
@@ -245,7 +249,7 @@ def _run_loopback(world, inputs, k, capacity=None, piece=None, opts=0, stats=Non
     for t in th:
         t.start()
     for t in th:
-        t.join(timeout=240)
+        t.join(timeout=timeout)
     alive = any(t.is_alive() for t in th)
     rs.set_multi_options(old_opts)
     if stats is not None:
@@ -308,35 +312,57 @@ def test_c_multi_loopback_local_error_on_every_rank():
     """a failure local to one rank (here rank 1 passes k_bits = 0) is carried in the
     status word of the first all-gather, so EVERY rank returns it together (RSORT_ERR_BITS)
     instead of the other ranks waiting in a collective that rank never joins."""
-    import threading
-    sys.path.insert(0, str(PKG))
-    import radixsort as rs
     world = 3
     inputs = [_loopback_inputs(r, 50_000, "uniform", False) for r in range(world)]
-    torch.cuda.set_device(0)
-    grp = rs.LoopbackGroup(world)
-    dev_in = [rs.from_numpy_u32(kx) for kx, _ in inputs]
-    res = [None] * world
-
-    def run(r):
-        torch.cuda.set_device(0)
-        st = torch.cuda.Stream()
-        try:
-            with torch.cuda.stream(st):
-                rs.multi_sort_device(grp.transport(r), dev_in[r], 0 if r == 1 else 8, capacity=200_000, stream=st)
-                st.synchronize()
-                res[r] = 0
-        except rs.RSortError as e:
-            res[r] = e.status
-
-    th = [threading.Thread(target=run, args=(r,)) for r in range(world)]
-    for t in th:
-        t.start()
-    for t in th:
-        t.join(timeout=60)
-    assert not any(t.is_alive() for t in th), "ranks left waiting"
-    grp.close()
+    res = _run_loopback(world, inputs, [0 if r == 1 else 8 for r in range(world)], capacity=200_000, timeout=60)
     assert res == [2] * world, res
+
+
+def test_c_multi_loopback_value_flags_disagree():
+    """Rank 1 sorts pairs (values and a values output), ranks 0 and 2 keys only: every rank sees the same flags in
+    the first all-gather and returns RSORT_ERR_ARG; nobody is left waiting."""
+    world = 3
+    inputs = [_loopback_inputs(r, 50_000, "uniform", r == 1) for r in range(world)]
+    res = _run_loopback(world, inputs, 8, capacity=200_000, timeout=60)
+    assert res == [1] * world, res
+
+
+def test_c_multi_loopback_workspace_too_small_on_every_rank():
+    """Rank 2's workspace is 256 B short of rsort_multi_workspace_size (still above the control buffers, so it
+    joins the first all-gather): its RSORT_ERR_WORKSPACE is carried there and every rank returns it."""
+    sys.path.insert(0, str(PKG))
+    import radixsort as rs
+    world, cap = 3, 200_000
+    inputs = [_loopback_inputs(r, 50_000, "uniform", False) for r in range(world)]
+    full = int(rs._lib().rsort_multi_workspace_size(inputs[2][0].size, cap, 8, 0, world))
+    res = _run_loopback(world, inputs, 8, capacity=cap, ws_bytes=[None, None, full - 256], timeout=60)
+    assert res == [7] * world, res
+
+
+def test_c_multi_workspace_below_the_control_buffers():
+    """A workspace that cannot even hold the collectives' control buffers is refused at once, before any
+    all-gather (world 1 only: at a larger world the peers would wait for this rank until the transport's limit)."""
+    sys.path.insert(0, str(PKG))
+    import radixsort as rs
+    inputs = [_loopback_inputs(0, 50_000, "uniform", False)]
+    res = _run_loopback(1, inputs, 8, opts=rs.MULTI_FULL, ws_bytes=[256], timeout=60)
+    assert res == [7], res
+
+
+@pytest.mark.parametrize("opts", [0, 1])
+def test_c_multi_loopback_world_1_whole_protocol(opts):
+    """One loopback rank with RSORT_MULTI_FULL runs every step (one half whatever the overlap flag: H = 2 needs
+    two ranks) and gives the oracle's output; without the flag the same input is sorted directly."""
+    sys.path.insert(0, str(PKG))
+    import radixsort as rs
+    inputs = [_loopback_inputs(0, 60_000, "hot", True)]
+    rk, rv = oracle_sort_pairs(inputs[0][0], inputs[0][1], 8)
+    for full, direct in ((rs.MULTI_FULL, 0), (0, 1)):
+        st = []
+        res = _run_loopback(1, inputs, 8, opts=full | (rs.MULTI_OVERLAP if opts else rs.MULTI_NO_OVERLAP), stats=st)
+        assert isinstance(res[0], tuple), res
+        assert np.array_equal(res[0][0], rk) and np.array_equal(res[0][1], rv) and res[0][2] == 0
+        assert st[0]["direct"] == direct and st[0]["halves"] == 1, st[0]
 
 
 @pytest.mark.parametrize("stage,opts", [(1, 0), (1, 1), (2, 0), (2, 1)])
@@ -382,19 +408,20 @@ def test_c_multi_loopback_stats(opts):
         assert [st[r]["send_keys"][p] for r in range(world)] == st[p]["recv_keys"]
 
 
-def test_c_multi_host_transport_threads():
-    """rsort_host_transport_wrap: the C protocol over a HOST-memory transport (the one bench.py's
-    gloo rehearsal uses), here three ranks as threads with a Python rendezvous; bit-exact as the
-    loopback, also with forced exchange rounds."""
+def _run_host_transport(world, inputs, k, trace=None, **kw):
+    """_run_loopback over rs.HostTransport: the ranks as threads with a Python rendezvous. trace: per rank a list
+    that receives its collectives in call order -- ("ag", bytes sent) for an all-gather, ("ex", bytes sent to each
+    rank, bytes expected from each rank) for an exchange."""
     import threading
     sys.path.insert(0, str(PKG))
     import radixsort as rs
-    world = 3
     bar = threading.Barrier(world, timeout=120)
     box = {}
 
     def mk(r):
         def allgather(send):
+            if trace is not None:
+                trace[r].append(("ag", len(send)))
             box[("ag", r)] = bytes(send)
             bar.wait()
             out = b"".join(box[("ag", q)] for q in range(world))
@@ -402,6 +429,8 @@ def test_c_multi_host_transport_threads():
             return out
 
         def exchange(sends, recv_sizes):
+            if trace is not None:
+                trace[r].append(("ex", [len(x) for x in sends], list(recv_sizes)))
             for p in range(world):
                 box[("ex", r, p)] = bytes(sends[p])
             bar.wait()
@@ -411,16 +440,139 @@ def test_c_multi_host_transport_threads():
         return rs.HostTransport(world, r, allgather, exchange)
 
     hts = [mk(r) for r in range(world)]
-    inputs = [_loopback_inputs(r, 150_000, "hot", True) for r in range(world)]
     try:
-        res = _run_loopback(world, inputs, 8, piece=20_000, transports=[h.transport for h in hts])
+        res = _run_loopback(world, inputs, k, transports=[h.transport for h in hts], **kw)
     finally:
         for h in hts:
             h.close()
     assert all(isinstance(x, tuple) for x in res), (res, [h.errors for h in hts])
+    return res
+
+
+def test_c_multi_host_transport_threads():
+    """rsort_host_transport_wrap: the C protocol over a HOST-memory transport (the one bench.py's
+    gloo rehearsal uses), here three ranks as threads with a Python rendezvous; bit-exact as the
+    loopback, also with forced exchange rounds."""
+    world = 3
+    inputs = [_loopback_inputs(r, 150_000, "hot", True) for r in range(world)]
+    res = _run_host_transport(world, inputs, 8, piece=20_000)
     rk, rv = oracle_sort_pairs(np.concatenate([i[0] for i in inputs]), np.concatenate([i[1] for i in inputs]), 8)
     assert np.array_equal(np.concatenate([x[0] for x in res]), rk)
     assert np.array_equal(np.concatenate([x[1] for x in res]), rv)
+
+
+# The collectives of three ranks, recorded from the library as it was BEFORE multi_sort became one function per
+# protocol step (this file's own `python tests/test_gpu_multi.py` against that commit's library, never from the
+# code under test): per case, per rank, the all-gathers and exchanges in call order with every byte count. Pins
+# the number and order of the collectives, the round cutting, the virtual-rank indexing (two halves: opts 1) and
+# the keys-then-values order inside a round.
+TRACE_WORLD, TRACE_N = 3, 60_000
+TRACE_CASES = (("hot", True, 4096, 0), ("hot", True, 4096, 1), ("empty0", False, None, 1))
+TRACES = {
+    "hot pairs piece 4096 opts 0": [
+        [('ag', 24), ('ag', 248252), ('ag', 272), ('ex', [0, 0, 15616], [0, 15616, 224]),
+         ('ex', [0, 0, 15616], [0, 15616, 224]), ('ex', [0, 0, 15616], [0, 15616, 0]),
+         ('ex', [0, 0, 15616], [0, 15616, 0]), ('ex', [0, 0, 15616], [0, 15616, 0]),
+         ('ex', [0, 0, 15616], [0, 15616, 0]), ('ex', [0, 0, 12948], [0, 15616, 0]),
+         ('ex', [0, 0, 12948], [0, 15616, 0]), ('ex', [0, 0, 0], [0, 1232, 0]), ('ex', [0, 0, 0], [0, 1232, 0]),
+         ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]),
+         ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0])],
+        [('ag', 24), ('ag', 248252), ('ag', 272), ('ex', [15616, 0, 15616], [0, 0, 15616]),
+         ('ex', [15616, 0, 15616], [0, 0, 15616]), ('ex', [15616, 0, 15616], [0, 0, 15616]),
+         ('ex', [15616, 0, 15616], [0, 0, 15616]), ('ex', [15616, 0, 15616], [0, 0, 15616]),
+         ('ex', [15616, 0, 15616], [0, 0, 15616]), ('ex', [15616, 0, 13968], [0, 0, 15616]),
+         ('ex', [15616, 0, 13968], [0, 0, 15616]), ('ex', [1232, 0, 0], [0, 0, 15616]),
+         ('ex', [1232, 0, 0], [0, 0, 15616]), ('ex', [0, 0, 0], [0, 0, 15616]), ('ex', [0, 0, 0], [0, 0, 15616]),
+         ('ex', [0, 0, 0], [0, 0, 15616]), ('ex', [0, 0, 0], [0, 0, 15616]), ('ex', [0, 0, 0], [0, 0, 15200]),
+         ('ex', [0, 0, 0], [0, 0, 15200])],
+        [('ag', 24), ('ag', 248252), ('ag', 272), ('ex', [224, 15616, 0], [15616, 15616, 0]),
+         ('ex', [224, 15616, 0], [15616, 15616, 0]), ('ex', [0, 15616, 0], [15616, 15616, 0]),
+         ('ex', [0, 15616, 0], [15616, 15616, 0]), ('ex', [0, 15616, 0], [15616, 15616, 0]),
+         ('ex', [0, 15616, 0], [15616, 15616, 0]), ('ex', [0, 15616, 0], [12948, 13968, 0]),
+         ('ex', [0, 15616, 0], [12948, 13968, 0]), ('ex', [0, 15616, 0], [0, 0, 0]), ('ex', [0, 15616, 0], [0, 0, 0]),
+         ('ex', [0, 15616, 0], [0, 0, 0]), ('ex', [0, 15616, 0], [0, 0, 0]), ('ex', [0, 15616, 0], [0, 0, 0]),
+         ('ex', [0, 15616, 0], [0, 0, 0]), ('ex', [0, 15200, 0], [0, 0, 0]), ('ex', [0, 15200, 0], [0, 0, 0])],
+    ],
+    "hot pairs piece 4096 opts 1": [
+        [('ag', 24), ('ag', 248252), ('ag', 272), ('ex', [0, 0, 15360], [0, 216, 224]),
+         ('ex', [0, 0, 15360], [0, 216, 224]), ('ex', [0, 0, 4348], [0, 0, 0]), ('ex', [0, 0, 4348], [0, 0, 0]),
+         ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]),
+         ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]),
+         ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]),
+         ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]),
+         ('ex', [0, 0, 15360], [0, 15360, 0]), ('ex', [0, 0, 15360], [0, 15360, 0]),
+         ('ex', [0, 0, 15360], [0, 15360, 0]), ('ex', [0, 0, 15360], [0, 15360, 0]),
+         ('ex', [0, 0, 9368], [0, 15360, 0]), ('ex', [0, 0, 9368], [0, 15360, 0]), ('ex', [0, 0, 0], [0, 15360, 0]),
+         ('ex', [0, 0, 0], [0, 15360, 0]), ('ex', [0, 0, 0], [0, 2040, 0]), ('ex', [0, 0, 0], [0, 2040, 0]),
+         ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]),
+         ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0])],
+        [('ag', 24), ('ag', 248252), ('ag', 272), ('ex', [216, 0, 15360], [0, 0, 2448]),
+         ('ex', [216, 0, 15360], [0, 0, 2448]), ('ex', [0, 0, 4752], [0, 0, 0]), ('ex', [0, 0, 4752], [0, 0, 0]),
+         ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]),
+         ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]),
+         ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]),
+         ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]),
+         ('ex', [15360, 0, 15360], [0, 0, 15360]), ('ex', [15360, 0, 15360], [0, 0, 15360]),
+         ('ex', [15360, 0, 15360], [0, 0, 15360]), ('ex', [15360, 0, 15360], [0, 0, 15360]),
+         ('ex', [15360, 0, 9984], [0, 0, 15360]), ('ex', [15360, 0, 9984], [0, 0, 15360]),
+         ('ex', [15360, 0, 0], [0, 0, 15360]), ('ex', [15360, 0, 0], [0, 0, 15360]),
+         ('ex', [2040, 0, 0], [0, 0, 15360]), ('ex', [2040, 0, 0], [0, 0, 15360]), ('ex', [0, 0, 0], [0, 0, 15360]),
+         ('ex', [0, 0, 0], [0, 0, 15360]), ('ex', [0, 0, 0], [0, 0, 15360]), ('ex', [0, 0, 0], [0, 0, 15360]),
+         ('ex', [0, 0, 0], [0, 0, 14544]), ('ex', [0, 0, 0], [0, 0, 14544])],
+        [('ag', 24), ('ag', 248252), ('ag', 272), ('ex', [224, 2448, 0], [15360, 15360, 0]),
+         ('ex', [224, 2448, 0], [15360, 15360, 0]), ('ex', [0, 0, 0], [4348, 4752, 0]),
+         ('ex', [0, 0, 0], [4348, 4752, 0]), ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]),
+         ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]),
+         ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]),
+         ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 0, 0], [0, 0, 0]),
+         ('ex', [0, 0, 0], [0, 0, 0]), ('ex', [0, 15360, 0], [15360, 15360, 0]),
+         ('ex', [0, 15360, 0], [15360, 15360, 0]), ('ex', [0, 15360, 0], [15360, 15360, 0]),
+         ('ex', [0, 15360, 0], [15360, 15360, 0]), ('ex', [0, 15360, 0], [9368, 9984, 0]),
+         ('ex', [0, 15360, 0], [9368, 9984, 0]), ('ex', [0, 15360, 0], [0, 0, 0]), ('ex', [0, 15360, 0], [0, 0, 0]),
+         ('ex', [0, 15360, 0], [0, 0, 0]), ('ex', [0, 15360, 0], [0, 0, 0]), ('ex', [0, 15360, 0], [0, 0, 0]),
+         ('ex', [0, 15360, 0], [0, 0, 0]), ('ex', [0, 15360, 0], [0, 0, 0]), ('ex', [0, 15360, 0], [0, 0, 0]),
+         ('ex', [0, 14544, 0], [0, 0, 0]), ('ex', [0, 14544, 0], [0, 0, 0])],
+    ],
+    "empty0 keys piece None opts 1": [
+        [('ag', 24), ('ag', 248252), ('ag', 272), ('ex', [0, 0, 0], [0, 40676, 41380]),
+         ('ex', [0, 0, 0], [0, 40684, 41384])],
+        [('ag', 24), ('ag', 248252), ('ag', 272), ('ex', [40676, 0, 40656], [0, 0, 41328]),
+         ('ex', [40684, 0, 40724], [0, 0, 41408])],
+        [('ag', 24), ('ag', 248252), ('ag', 272), ('ex', [41380, 41328, 0], [0, 40656, 0]),
+         ('ex', [41384, 41408, 0], [0, 40724, 0])],
+    ],
+}
+
+
+def _trace_key(dist_name, pairs, piece, opts):
+    return f"{dist_name} {'pairs' if pairs else 'keys'} piece {piece} opts {opts}"
+
+
+def _traced_sort(dist_name, pairs, piece, opts):
+    inputs = [_loopback_inputs(r, TRACE_N, dist_name, pairs) for r in range(TRACE_WORLD)]
+    trace = [[] for _ in range(TRACE_WORLD)]
+    res = _run_host_transport(TRACE_WORLD, inputs, 8, trace=trace, piece=piece, opts=opts)
+    return inputs, res, trace
+
+
+@pytest.mark.parametrize("dist_name,pairs,piece,opts", TRACE_CASES)
+def test_c_multi_collective_trace(dist_name, pairs, piece, opts):
+    """Every rank's collectives, in order and byte for byte, are the recorded ones (TRACES); the output is still
+    the oracle's."""
+    inputs, res, trace = _traced_sort(dist_name, pairs, piece, opts)
+    want = TRACES[_trace_key(dist_name, pairs, piece, opts)]
+    for r in range(TRACE_WORLD):
+        assert trace[r] == want[r], (r, trace[r])
+    if piece:  # (the case is there for its several rounds: more exchanges than arrays x halves)
+        assert all(sum(c[0] == "ex" for c in t) > (2 if pairs else 1) * (2 if opts else 1) for t in trace)
+    keys = np.concatenate([i[0] for i in inputs])
+    if pairs:
+        rk, rv = oracle_sort_pairs(keys, np.concatenate([i[1] for i in inputs]), 8)
+        assert np.array_equal(np.concatenate([x[0] for x in res]), rk)
+        assert np.array_equal(np.concatenate([x[1] for x in res]), rv)
+    else:
+        assert np.array_equal(np.concatenate([x[0] for x in res]), oracle_sort(keys, 8))
+    assert [x[2] for x in res] == list(np.cumsum([0] + [x[0].size for x in res[:-1]]))
 
 
 @pytest.mark.parametrize("world,dist_name,pairs,k,piece", [(2, "uniform", False, 8, None), (3, "hot", True, 8, None),
@@ -582,3 +734,13 @@ def test_rccl_comm_timeout_setting():
         assert rs.set_comm_timeout(0) == 1234  # (<= 0 leaves it unchanged)
     finally:
         rs.set_comm_timeout(old)
+
+
+if __name__ == "__main__":  # the TRACES literal above, from the library as built
+    print("TRACES = {")
+    for case in TRACE_CASES:
+        print(f'    "{_trace_key(*case)}": [')
+        for t in _traced_sort(*case)[2]:
+            print(f"        {t},")
+        print("    ],")
+    print("}")

@@ -11,7 +11,9 @@ partition that is the point -- its plan has no next-digit tables, whatever its b
 
 The families `segmented`, `topk` and `topk_rows` (rsort_segmented_workspace_size, rsort_topk_workspace_size with the
 route given, rsort_topk_rows_workspace_size) were recorded the same way from the commit before those three layouts
-and the sort's became walks over one allocator; seg_walk() and rows_walk() restate the two simple ones."""
+and the sort's became walks over one allocator; seg_walk() and rows_walk() restate the two simple ones. The `multi`
+rows of worlds 1, 2, 3 and 16 were recorded from the commit before the multi-GPU driver's layout (multi_bytes in
+csrc/rsort_multi.cpp) became a walk over that allocator too."""
 import json
 import os
 import subprocess
@@ -24,6 +26,7 @@ KS = (1, 3, 4, 5, 8, 11, 13)
 BUCKETS = (2, 8, 17, 32)
 MULTI_NS = tuple(n for n in NS if n <= 1 << 30)
 MULTI_WORLD = 8
+MULTI_MORE_WORLDS = (1, 2, 3, 16)  # (the gathered sample, and the room to sort it, grow with the world)
 # tiles_per_chunk of a sort plan: the library's own choice (0), one tile per chunk (k = 4 at 2^22 + 9 keys: 1025
 # chunks, raw next-digit tables; at 2^23 + 9: 2049, tail scans), and 256 chunks where n has the tiles for them
 # (k = 8 on line tiles: the digit-group plans)
@@ -74,11 +77,12 @@ def compute():
         for pairs in (0, 1):
             out["partition"][f"b{nb} {'pairs' if pairs else 'keys'}"] = [
                 int(lib.rsort_partition_workspace_size(n, nb, pairs)) for n in NS]
-    for k in (8, 4):
-        for pairs in (0, 1):
-            out["multi"][f"k{k} {'pairs' if pairs else 'keys'}"] = [
-                int(lib.rsort_multi_workspace_size(n, rs.default_capacity(n), k, pairs, MULTI_WORLD))
-                for n in MULTI_NS]
+    for world in (MULTI_WORLD,) + MULTI_MORE_WORLDS:
+        for k in (8, 4):
+            for pairs in (0, 1):
+                key = f"k{k} {'pairs' if pairs else 'keys'}" + (f" world {world}" if world != MULTI_WORLD else "")
+                out["multi"][key] = [int(lib.rsort_multi_workspace_size(n, rs.default_capacity(n), k, pairs, world))
+                                     for n in MULTI_NS]
     for pairs in (0, 1):
         kind = "pairs" if pairs else "keys"
         for nseg in SEG_NSEGS:
@@ -166,6 +170,22 @@ SIZES = {
         "k8 pairs": [110682880, 110684928, 112515328, 113685248, 186497792, 262102784, 337652480, 186495744, 1319125760, 19438542592],
         "k4 keys": [76029952, 76030208, 76430080, 76685568, 92807424, 113861120, 151619328, 92807168, 642355968, 9702054912],
         "k4 pairs": [76029952, 76030464, 76830208, 77341184, 114068736, 189565952, 265065728, 114067456, 1246533888, 19365927936],
+        "k8 keys world 1": [81060608, 81062144, 81992704, 82587904, 119236864, 156872960, 194784000, 119235328, 685501184, 9745241856],
+        "k8 pairs world 1": [81322752, 81324800, 83155200, 84325120, 157137664, 232742656, 308292352, 157135616, 1289765632, 19409182464],
+        "k4 keys world 1": [17047552, 17047808, 17447680, 17703168, 46753024, 84500992, 122259200, 46751744, 612995840, 9672694784],
+        "k4 pairs world 1": [17047552, 17048064, 17847808, 18358784, 84708608, 160205824, 235705600, 84707328, 1217173760, 19336567808],
+        "k8 keys world 2": [85254912, 85256448, 86187008, 86782208, 123431168, 161067264, 198978304, 123429632, 689695488, 9749436160],
+        "k8 pairs world 2": [85517056, 85519104, 87349504, 88519424, 161331968, 236936960, 312486656, 161329920, 1293959936, 19413376768],
+        "k4 keys world 2": [25698304, 25698560, 26098432, 26353920, 50947328, 88695296, 126453504, 50946048, 617190144, 9676889088],
+        "k4 pairs world 2": [25698304, 25698816, 26498560, 27009536, 88902912, 164400128, 239899904, 88901632, 1221368064, 19340762112],
+        "k8 keys world 3": [89449216, 89450752, 90381312, 90976512, 127625472, 165261568, 203172608, 127623936, 693889792, 9753630464],
+        "k8 pairs world 3": [89711360, 89713408, 91543808, 92713728, 165526272, 241131264, 316680960, 165524224, 1298154240, 19417571072],
+        "k4 keys world 3": [33955840, 33956096, 34355968, 34611456, 55141632, 92889600, 130647808, 55140352, 621384448, 9681083392],
+        "k4 pairs world 3": [33955840, 33956352, 34756096, 35267072, 93097216, 168594432, 244094208, 93095936, 1225562368, 19344956416],
+        "k8 keys world 16": [143975168, 143976704, 144907264, 145502464, 182151424, 219787520, 257698560, 182149888, 748415744, 9808156416],
+        "k8 pairs world 16": [144237312, 144239360, 146069760, 147239680, 220052224, 295657216, 371206912, 220050176, 1352680192, 19472097024],
+        "k4 keys world 16": [143138816, 143139072, 143538944, 143794432, 159916288, 176693504, 193470464, 159916032, 675910400, 9735609344],
+        "k4 pairs world 16": [143138816, 143139328, 143939072, 144450048, 176693760, 223120384, 298620160, 176693248, 1280088320, 19399482368],
     },
     "segmented": {
         "nseg0 keys": [256, 512, 400384, 655872, 16777728, 33554944, 50331904, 16777472, 268435712, 4294967552, 17179869440],
