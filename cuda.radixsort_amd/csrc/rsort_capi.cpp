@@ -31,6 +31,21 @@ std::atomic<int> g_rank_algo{RSORT_RANK_MATCH};
 std::atomic<int> g_group_chunks{1};
 std::atomic<int> g_table_fault{0};  // rsort_inject_table_fault (tests)
 std::atomic<int> g_rank_fault{0};   // rsort_inject_rank_fault (tests)
+// rsort_inject_fault_window (tests): which of the calling thread's sort calls (entries into sort_planned, numbered
+// from 0 since the window was set) see the two hooks above; count < 0: no window, every one does
+struct FaultWindow {
+    int64_t first = 0, count = -1, started = 0;
+};
+thread_local FaultWindow t_fault_window;
+// numbers this sort call; true when the hooks apply to it
+bool fault_window_admits() {
+    FaultWindow &w = t_fault_window;
+    const int64_t i = w.started++;
+    return w.count < 0 || (i >= w.first && i - w.first < w.count);
+}
+// the rank hook for what is no sort call (the partition's scatter, a single pass, the segmented sort): in no
+// window, so it applies only while the calling thread has none
+uint32_t rank_fault_unnumbered() { return (t_fault_window.count < 0 && g_rank_fault.load()) ? 1u : 0u; }
 std::atomic<int> g_hybrid{RSORT_HYBRID_AUTO};  // rsort_set_hybrid
 std::atomic<int> g_seg_grid_limit{0};  // rsort_set_segmented_grid_limit (tests); 0: no limit
 
@@ -301,7 +316,7 @@ ScatterArgs scatter_args(const rsort_plan &p, const PassIo &io, int shift, const
     a.chunk_keys = (uint64_t)p.chunk_keys;
     a.num_chunks = (uint32_t)p.num_chunks;
     a.shift = (uint32_t)shift;
-    a.rank_fault = g_rank_fault.load() ? 1u : 0u;
+    a.rank_fault = rank_fault_unnumbered();  // (a sort's passes take their sort call's: SortCtx::scatter)
     return a;
 }
 
@@ -463,6 +478,8 @@ struct SortCtx {
     Gate lsd;
     const uint32_t *sk, *sv;
     uint32_t *kout, *vout;
+    uint32_t rank_fault;  // the test hooks, as this sort call sees them (rsort_inject_fault_window)
+    bool table_fault;
 
     HistArgs hist(int i, uint32_t *table) const { return gated(hist_args(p, sk, i * p.k_bits, table), lsd); }
     ScanArgs scan(uint32_t *table) const { return gated(scan_args(p, table, c.bsums), lsd); }
@@ -471,6 +488,7 @@ struct SortCtx {
         const PassIo io{sk, sv, to_out ? kout : c.tmp_k, to_out ? vout : c.tmp_v};
         ScatterArgs a = gated(scatter_args(p, io, i * p.k_bits, table), lsd);
         a.check = c.done + kDoneErr;
+        a.rank_fault = rank_fault;
         return a;
     }
     // runs a pass's scatter; what it wrote is the next pass's input
@@ -505,7 +523,7 @@ int SortCtx::hybrid_prologue() {
     h.n = (uint64_t)p.n;
     h.threshold = gate_threshold(p.n);
     h.force = force ? 1u : 0u;
-    h.rank_fault = g_rank_fault.load() ? 1u : 0u;
+    h.rank_fault = rank_fault;
     hyb_note_bucket();
     {
         // the one clear of the joint counts, with the rows counter and the gate's flag behind them: the LSD
@@ -527,10 +545,12 @@ int SortCtx::hybrid_prologue() {
     if ((st = run_scan(p, gated(scan_args(p, c.table, c.bsums), run), s))) return st;
     ScatterArgs pa = gated(scatter_args(p, PassIo{sk, nullptr, kout, nullptr}, 24, c.table), run);
     pa.check = c.done + kDoneErr;
+    pa.rank_fault = rank_fault;
     if ((st = run_scatter(p, pa, kDigitShift, s))) return st;
     ScatterArgs pb = gated(scatter_args(p, PassIo{kout, nullptr, c.tmp_k, nullptr}, 16, c.joint), run);
     pb.bounds = hb;
     pb.check = c.done + kDoneErr;
+    pb.rank_fault = rank_fault;
     if ((st = run_scatter(p, pb, kDigitShift, s))) return st;
     const int cus = std::max(1, device_cus());
     const int bpc = std::max(1, hyb_blocks_per_cu());
@@ -650,7 +670,7 @@ int SortCtx::next_digit_passes(bool rawt) {
         if ((st = run_pass(a))) return st;
         // test hook: corrupt the raw table pass 1 reads (its total is then not n: every pass-1 workgroup
         // writes nothing and records the failure for rsort_plan_check / RSORT_ERR_CHECK)
-        if (i == 0 && rawt && nxt && g_table_fault.load() &&
+        if (i == 0 && rawt && nxt && table_fault &&
             hipMemsetD32Async((hipDeviceptr_t)nxt, 0xFFFFFFFFu, 1, s) != hipSuccess)
             return RSORT_ERR_HIP;
     }
@@ -659,6 +679,7 @@ int SortCtx::next_digit_passes(bool rawt) {
 
 int sort_planned(const rsort_plan &p, const uint32_t *kin, const uint32_t *vin, uint32_t *kout,
                  uint32_t *vout, void *ws, size_t wsb, hipStream_t s, bool allow_hybrid = true) {
+    const bool faults = fault_window_admits();  // (every entry is a numbered sort call, whatever it then does)
     int st = check_plan(&p);
     if (st) return st;
     if (p.n == 0) return RSORT_OK;
@@ -666,7 +687,8 @@ int sort_planned(const rsort_plan &p, const uint32_t *kin, const uint32_t *vin, 
     if (!aligned4(kin) || !aligned4(kout) || (p.pairs && (!aligned4(vin) || !aligned4(vout))))
         return RSORT_ERR_ALIGN;
     if (wsb < p.workspace_bytes) return RSORT_ERR_WORKSPACE;
-    SortCtx x{p, carve(p, ws), s, Gate{}, kin, vin, kout, vout};
+    SortCtx x{p, carve(p, ws), s, Gate{}, kin, vin, kout, vout,
+              (faults && g_rank_fault.load()) ? 1u : 0u, faults && g_table_fault.load() != 0};
     const Carve &c = x.c;
     const bool inplace = (kin == kout) || (p.pairs && vin == vout);
     if (inplace && (p.passes % 2 == 1)) {
@@ -897,7 +919,7 @@ int seg_sort(const uint32_t *kin, const uint32_t *vin, uint32_t *kout, uint32_t 
         a.list = c.lists[kind];
         a.count = c.counters + kind;
         a.check = c.counters + kSegCheckWord;
-        a.rank_fault = g_rank_fault.load() ? 1u : 0u;
+        a.rank_fault = rank_fault_unnumbered();
         if ((st = hip_status(launch_seg_sort(kind, pairs, rank, a, grid, s)))) return st;
     }
     return RSORT_OK;
@@ -1031,6 +1053,12 @@ int topk_check(int size_st, bool nothing, const void *kin, const void *vin, int 
     return RSORT_OK;
 }
 
+// In front of the sort a call runs, behind the memset of its state words: that sort's check word is the call's
+// (rsort_topk_report; a call that runs none leaves the word as its memset left it, 0).
+int topk_mark_sorted(const TopkCarve &c, hipStream_t s) {
+    return hip_status(hipMemsetD32Async((hipDeviceptr_t)(c.state + kTkSorted), 1, 1, s));
+}
+
 int topk_select(const uint32_t *kin, const uint32_t *vin, int64_t n, int64_t k, int flags, uint32_t *kout,
                 uint32_t *vout, const TopkCarve &c, const rsort_plan &plan, hipStream_t s) {
     const int pairs = vout != nullptr;
@@ -1091,6 +1119,7 @@ int topk_select(const uint32_t *kin, const uint32_t *vin, int64_t n, int64_t k, 
         cp.vin = c.wv;
         cp.vout = vout;
     } else {
+        if ((st = topk_mark_sorted(c, s))) return st;
         if ((st = sort_planned(plan, c.wk, c.wv, kout, vout, c.sort_ws, c.sort_bytes, s))) return st;
         if (m == 0) return RSORT_OK;
         cp.kin = kout;  // the sorted x back to keys, in place
@@ -1107,6 +1136,7 @@ int topk_sort(const uint32_t *kin, const uint32_t *vin, int64_t n, int64_t k, in
     const bool pairs = vout != nullptr, largest = (flags & RSORT_TOPK_LARGEST) != 0;
     int st;
     if (hipMemsetAsync(c.state, 0xFF, 256, s) != hipSuccess) return RSORT_ERR_HIP;
+    if ((st = topk_mark_sorted(c, s))) return st;
     const uint32_t *ks = kin, *vs = vin;
     if (pairs && largest) {
         PhaseScope ps(RSORT_PHASE_COPY, n, s);
@@ -1163,6 +1193,28 @@ size_t topk_workspace_size(int64_t n, int64_t k, int pairs, int route) {
     return topk_carve(n, k, pairs, route, plan, nullptr).bytes;
 }
 
+// report8 (rsort_topk_report) of the call for (n, k, pairs) that last ran in ws, k > 0. The state words come first
+// whatever the layout behind them; the sort's workspace is found from the route the call recorded.
+int topk_read_report(int64_t n, int64_t k, int pairs, void *ws, int64_t *report8, hipStream_t s) {
+    const rsort_plan none{};
+    const TopkCarve c0 = topk_carve(0, 0, 0, RSORT_TOPK_SORT, none, ws);
+    uint32_t h[kTkSorted + 1] = {0};
+    int st;
+    if ((st = read_words(h, c0.state, kTkSorted + 1, s))) return st;
+    const int route = (int)h[kTkRoute];
+    const bool sorted = route == RSORT_TOPK_SORT;
+    for (int i = 0; i < 8; ++i) report8[i] = 0;
+    for (int i = 0; i < 6; ++i) report8[i] = (sorted && i >= 2) ? -1 : (int64_t)h[i];
+    if (h[kTkSorted] != 1u || (route != RSORT_TOPK_SELECT && route != RSORT_TOPK_SORT)) return RSORT_OK;
+    rsort_plan plan;
+    if ((st = topk_plan(n, k, pairs, route, &plan))) return st;
+    const TopkCarve c = topk_carve(n, k, pairs, route, plan, ws);
+    uint32_t check = 0;
+    if ((st = read_words(&check, sort_check_word(plan, c.sort_ws), 1, s))) return st;
+    report8[6] = (int64_t)(check & (kCheckTable | kCheckRankOrder));
+    return RSORT_OK;
+}
+
 int topk_host(const uint32_t *kin, const uint32_t *vin, int64_t n, int64_t k, int flags, uint32_t *kout,
               uint32_t *vout) {
     bool noop;
@@ -1179,7 +1231,10 @@ int topk_host(const uint32_t *kin, const uint32_t *vin, int64_t n, int64_t k, in
     if ((st = h.upload(d_kin, kin, nw)) || (st = h.upload(d_vin, vin, nw))) return st;
     if ((st = topk_device(d_kin, d_vin, n, k, flags, d_kout, d_vout, ws, wsb, h.s))) return h.drain(st);
     if ((st = h.download(kout, d_kout, kw)) || (st = h.download(vout, d_vout, kw))) return st;
-    return hip_status(hipStreamSynchronize(h.s));
+    // this entry waits for the device anyway: the self-checks of the sort the call ran are read here
+    int64_t rep[8];
+    if ((st = topk_read_report(n, k, pairs, ws, rep, h.s))) return st;
+    return rep[6] ? RSORT_ERR_CHECK : RSORT_OK;
 }
 
 // ------------------------------------------------------------------------------ row-wise top-k
@@ -1330,6 +1385,10 @@ int set_grid_limit(std::atomic<int> &limit, int workgroups) {
 }  // namespace
 
 void rsort::profile_pause(int delta) { t_prof_paused += delta; }
+
+const uint32_t *rsort::sort_check_word(const rsort_plan &p, const void *ws) {
+    return carve(p, const_cast<void *>(ws)).done + kDoneErr;
+}
 
 // ================================================================================ C ABI
 extern "C" {
@@ -1493,19 +1552,12 @@ int rsort_u32_topk(const uint32_t *keys, const uint32_t *vals, int64_t n, int64_
 
 int rsort_topk_report(int64_t n, int64_t k, int pairs, const void *d_workspace, int64_t *report8, void *stream) {
     int st;
-    (void)pairs;  // (the state words come first in the workspace whatever the layout behind them)
     if (!report8) return RSORT_ERR_ARG;
     for (int i = 0; i < 8; ++i) report8[i] = 0;
     if ((st = topk_sizes(n, k))) return st;
     if (k == 0) return RSORT_OK;
     if (!d_workspace) return RSORT_ERR_ARG;
-    const rsort_plan none{};
-    const TopkCarve c = topk_carve(0, 0, 0, RSORT_TOPK_SORT, none, const_cast<void *>(d_workspace));
-    uint32_t h[8] = {0};
-    if ((st = read_words(h, c.state, 8, (hipStream_t)stream))) return st;
-    const bool sorted = h[kTkRoute] == (uint32_t)RSORT_TOPK_SORT;
-    for (int i = 0; i < 6; ++i) report8[i] = (sorted && i >= 2) ? -1 : (int64_t)h[i];
-    return RSORT_OK;
+    return topk_read_report(n, k, pairs ? 1 : 0, const_cast<void *>(d_workspace), report8, (hipStream_t)stream);
 }
 
 int rsort_set_topk_route(int route) {
@@ -1733,6 +1785,14 @@ int rsort_plan_features(const rsort_plan *plan) {
 int rsort_inject_table_fault(int enable) { return g_table_fault.exchange(enable ? 1 : 0); }
 
 int rsort_inject_rank_fault(int enable) { return g_rank_fault.exchange(enable ? 1 : 0); }
+
+int rsort_inject_fault_window(int64_t first, int64_t count) {
+    if (count >= 0 && first < 0) return RSORT_ERR_ARG;
+    t_fault_window = FaultWindow{count < 0 ? 0 : first, count < 0 ? -1 : count, 0};
+    return RSORT_OK;
+}
+
+int64_t rsort_fault_window_calls(void) { return t_fault_window.started; }
 
 int rsort_plan_check(const rsort_plan *plan, const void *d_workspace, int *flags, void *stream) {
     if (!plan || !flags || !d_workspace) return RSORT_ERR_ARG;

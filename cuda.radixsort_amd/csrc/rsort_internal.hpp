@@ -308,6 +308,9 @@ void profile_pause(int delta);
 // n (next-digit plans); kCheckRankOrder -- a lane-ordered scatter kernel's per-tile rank check failed.
 constexpr uint32_t kDoneErr = 1;
 constexpr uint32_t kCheckTable = 1u, kCheckRankOrder = 2u;
+// Where the check word of a sort with plan `p` lies in its workspace `ws` (the host driver's carve): for the
+// callers that keep it past the workspace's next user (the multi-GPU sort's halves share one workspace).
+const uint32_t *sort_check_word(const rsort_plan &p, const void *ws);
 
 // ------------------------------------------------------------------------------ hybrid route
 // (rsort_hybrid.hip; sort_planned in rsort_capi.cpp.) Keys-only k = 8 sorts of ~2^29..2^30 keys whose top 16
@@ -416,8 +419,10 @@ constexpr uint32_t kTopkBins0 = 256, kTopkBins = 4096;
 constexpr uint32_t kTopkTotalsWords = kTopkBins0 + 2 * kTopkBins;  // the bin totals of levels 0, 1, 2
 // The call's 256 B of state, first in the workspace (rsort_topk_report reads words 0..7). A SELECT call clears
 // it with the totals; a SORT call fills it with ~0 and writes the route, the k-th key and the reserved words.
+// kTkSorted: the host sets it to 1 (a memset node) in front of the sort the call runs -- the finishing sort of k,
+// or the whole sort -- so rsort_topk_report reads that sort's check word only where one ran (as kTrSorted).
 enum TopkWord : uint32_t { kTkRoute = 0, kTkKth = 1, kTkBefore = 2, kTkTaken = 3, kTkEqual = 4, kTkCand = 5,
-                           kTkKrem = 8, kTkPrefix = 9, kTkBelow0 = 10, kTkWords = 64 };
+                           kTkKrem = 8, kTkPrefix = 9, kTkBelow0 = 10, kTkSorted = 11, kTkWords = 64 };
 struct TopkArgs {
     const uint32_t *kin, *vin;   // the input (vin == nullptr: keys only, or indices)
     uint32_t *state, *totals;

@@ -107,11 +107,15 @@ constexpr size_t kNWords = 3, kNStatusWord = 2;
 // step 4's: the bucket counts in [0, buckets), then the capacity and the local status at fixed words
 constexpr size_t kRowWords = kMaxBuckets + 2, kCapWord = kMaxBuckets, kStatusWord = kMaxBuckets + 1;
 
+// the local sorts of one call: one per half (the direct sort takes the first slot)
+constexpr int kCheckSlots = 2;
+
 struct MultiCarve {
     uint32_t *part_k, *part_v;
     uint64_t *n_send, *n_all;      // [kNWords], [world][kNWords]
     uint64_t *c_send, *c_all;      // [kRowWords], [world][kRowWords]: counts, capacity, status
     uint32_t *starts;              // [kMaxBuckets + 1]
+    uint32_t *checks;              // [kCheckSlots]: every local sort's check word, copied behind that sort
     uint32_t *samp_send, *samp_all;  // [kSampleBudget + 1], [world][...]: the sample row + the status
     size_t control_bytes;          // the buffers above part_k
     void *sub;                     // partition, sample sort and local sort, in turn
@@ -141,6 +145,7 @@ size_t multi_bytes(int64_t n, int64_t cap, int k, int pairs, int world, MultiCar
     m.c_send = (uint64_t *)b.take(kRowWords * 8);
     m.c_all = (uint64_t *)b.take((size_t)kMaxRanks * kRowWords * 8);
     m.starts = b.take((size_t)(kMaxBuckets + 1) * 4);
+    m.checks = b.take((size_t)kCheckSlots * 4);
     m.samp_send = b.take((size_t)(kSampleBudget + 1) * 4);
     m.samp_all = b.take((size_t)world * (kSampleBudget + 1) * 4);
     m.control_bytes = b.off;
@@ -533,6 +538,23 @@ int check_args(MultiCall &c, void *ws, size_t workspace_bytes) {
     return RSORT_OK;
 }
 
+// The local sorts' self-checks. The halves sort one after the other in the same workspace (m.sub), and pass 0 of a
+// sort clears the check word the sort before it set: each sort's word is copied into its slot of the control area
+// right behind it, on its stream, and the slots are read once when all have run.
+int clear_checks(MultiCall &c) { return hip_status(hipMemsetAsync(c.m.checks, 0, (size_t)kCheckSlots * 4, c.s)); }
+int keep_check(MultiCall &c, const rsort_plan &p, int slot, hipStream_t ss) {
+    return hip_status(hipMemcpyAsync(c.m.checks + slot, sort_check_word(p, c.m.sub), 4, hipMemcpyDeviceToDevice, ss));
+}
+// waits for the local sorts (the call's last synchronisation of `s`): RSORT_ERR_CHECK when any of them failed
+int read_checks(MultiCall &c) {
+    uint32_t h[kCheckSlots] = {0};
+    int st;
+    if ((st = read_words(h, c.m.checks, kCheckSlots, c.s))) return st;
+    for (uint32_t w : h)
+        if (w & (kCheckTable | kCheckRankOrder)) return RSORT_ERR_CHECK;
+    return RSORT_OK;
+}
+
 // One rank without RSORT_MULTI_FULL: the partition would be one bucket (a copy) and the exchange a self copy, so the
 // keys go straight through the local sort (same output, no peers to agree with).
 int sort_direct(MultiCall &c) {
@@ -541,11 +563,14 @@ int sort_direct(MultiCall &c) {
     c.timer.mark(MultiTimer::kExchange);  // (nothing exchanged: the whole time is the local sort)
     int st;
     rsort_plan p;
+    if ((st = clear_checks(c))) return st;
     // (the multi-GPU path's local sorts never take the hybrid route: said here, not left to its gate)
     if (c.n > 0 && ((st = rsort_plan_make(c.n, c.k_bits, c.pairs, 0, &p)) ||
                     (st = rsort_sort_planned_ex(&p, c.keys, c.vals, c.keys_out, c.vals_out, c.m.sub, c.m.sub_bytes, c.s,
-                                                RSORT_SORT_NO_HYBRID))))
+                                                RSORT_SORT_NO_HYBRID)) ||
+                    (st = keep_check(c, p, 0, c.s))))
         return st;
+    if ((st = read_checks(c))) return st;
     *c.out_n = c.n;
     *c.out_offset = 0;
     c.stats.direct = c.stats.halves = 1;
@@ -593,6 +618,12 @@ int sample_quantiles(MultiCall &c, const rsort_sample_plan &sp, uint32_t *q, int
     profile_pause(1);  // (its passes are part of the plan phase, not the measured local sort)
     c.local = rsort_u32_device(m.samp_all, m.samp_all, ns, 8, m.sub, m.sub_bytes, c.s);
     profile_pause(-1);
+    // its self-check, read with the quantile keys below (an unstable sample sort gives unsorted quantiles)
+    uint32_t check = 0;
+    rsort_plan sort_plan;
+    if (!c.local) c.local = rsort_plan_make(ns, 8, 0, 0, &sort_plan);  // (rsort_u32_device's plan)
+    if (!c.local && hipMemcpyAsync(&check, sort_check_word(sort_plan, m.sub), 4, hipMemcpyDeviceToHost, c.s) != hipSuccess)
+        c.local = RSORT_ERR_HIP;
     // each quantile key and the samples hot_reach away on both sides: the key is hot (its own equal-keys bucket,
     // rsort_multi_splitters_make_hot) when either is the same key
     const int64_t L = std::max<int64_t>(1, sp.total / ((int64_t)c.V * 128));
@@ -609,6 +640,7 @@ int sample_quantiles(MultiCall &c, const rsort_sample_plan &sp, uint32_t *q, int
         }
     }
     if (!c.local && hipStreamSynchronize(c.s) != hipSuccess) c.local = RSORT_ERR_HIP;
+    if (!c.local && (check & (kCheckTable | kCheckRankOrder))) c.local = RSORT_ERR_CHECK;
     for (int i = 1; i < c.V && !c.local; ++i) {
         const int64_t qi = rsort_multi_quantile_index(&sp, i);
         hot[i - 1] = (qi - L >= 0 && nb[i - 1][0] == q[i - 1]) || (qi + L < sp.total && nb[i - 1][1] == q[i - 1]);
@@ -716,7 +748,7 @@ int exchange_half(MultiCall &c, SideScope &side, const rsort_exchange_plan &xs, 
 
 // 6. local sort of the n keys that arrived in ok / ov, in place; beside: on the side stream, while the next half is
 //    exchanged on `s` (the side stream then holds work, so that half's own copy stays on `s`)
-int sort_half(MultiCall &c, SideScope &side, int64_t n, uint32_t *ok, uint32_t *ov, bool beside) {
+int sort_half(MultiCall &c, SideScope &side, int64_t n, uint32_t *ok, uint32_t *ov, int slot, bool beside) {
     if (n <= 0) return RSORT_OK;
     int st;
     rsort_plan p;
@@ -724,7 +756,12 @@ int sort_half(MultiCall &c, SideScope &side, int64_t n, uint32_t *ok, uint32_t *
     const hipStream_t ss = beside ? side.fork() : c.s;
     // (a rank's keys cover 1 / N of the key space: their (digit 3, digit 2) buckets would overflow)
     if ((st = rsort_sort_planned_ex(&p, ok, ov, ok, ov, c.m.sub, c.m.sub_bytes, ss, RSORT_SORT_NO_HYBRID))) return st;
-    return ss != c.s ? side.mark() : RSORT_OK;
+    st = keep_check(c, p, slot, ss);
+    if (ss != c.s) {  // (the side stream holds the sort whether or not the copy went in behind it)
+        const int marked = side.mark();
+        if (!st) st = marked;
+    }
+    return st;
 }
 
 // 5-6. per half: the exchange, then the local sort of what arrived (the first half's beside the second's exchange)
@@ -742,6 +779,7 @@ int exchange_and_sort(MultiCall &c, const rsort_exchange_plan *xv) {
             c.stats.send_keys[p] += xs.send_cnt[p * H + h];
             c.stats.recv_keys[p] += xv[me * H + h].recv_cnt[p * H];
         }
+    if ((st = clear_checks(c))) return st;
     SideScope side(c.s);  // (every return below leaves through its destructor)
     int64_t base = 0;
     for (int h = 0; h < H; ++h) {
@@ -754,10 +792,11 @@ int exchange_and_sort(MultiCall &c, const rsort_exchange_plan *xv) {
         if (last && H > 1) c.timer.mark(MultiTimer::kExchange);
         if ((st = side.join())) return st;
         if (last && H == 1) c.timer.mark(MultiTimer::kExchange);
-        if ((st = sort_half(c, side, xd.n_recv, ok, ov, !last))) return st;
+        if ((st = sort_half(c, side, xd.n_recv, ok, ov, h, !last))) return st;
         base += xd.n_recv;
     }
     if ((st = side.join())) return st;
+    if ((st = read_checks(c))) return st;
     *c.out_n = c.stats.n_out = base;
     *c.out_offset = xs.offset;
     return c.timer.finish(c.stats);

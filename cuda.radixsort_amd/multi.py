@@ -10,18 +10,22 @@ rsort_multi_splitters_make, rsort_multi_exchange_plan), so both paths split and 
   3. splitters with an equal-keys bucket per hot quantile key: a run of equal keys --
      a hot key, duplicate-heavy input -- is split across ranks in (source rank, position) order
   4. stable partition into those buckets (HIP: rsort_partition_device)
-  5. all_gather of the bucket counts and capacities    -> the exchange plan, the same on every
-     rank (a capacity overflow raises on ALL ranks before any key moves)
+  5. all_gather of the bucket counts, capacities and self-check results -> the exchange plan, the
+     same on every rank (a capacity overflow, or a sample sort or partition that failed its
+     on-device self-check on any rank, raises on ALL ranks before any key moves)
   6. the exchange: own range by a device copy, every other message by all_to_all (RCCL over
      xGMI: grouped send/recv), in equal rounds of <= 2^28 keys per message
-  7. local LSD sort of what arrived (HIP)
+  7. local LSD sort of what arrived (HIP); its self-check raises on the rank it failed on
 
 Rank r ends with the keys of global ranks [offset_r, offset_r + count_r); concatenating the
 ranks' outputs in rank order gives exactly Baseline1's sorted array. Received chunks are placed
 in source-rank order, so with values the whole sort stays stable.
 
 The per-device steps go through an `ops` object: GpuOps (the product) calls librsort.so; the CPU
-tests substitute a numpy restatement to exercise the distributed logic with gloo.
+tests substitute a numpy restatement to exercise the distributed logic with gloo. ops.check(step)
+gives the self-check flags (rs.CHECK_* bits, 0 = clean) of the step it last ran: "sample" (sort_keys),
+"partition" or "sort". An ops object without a check method runs no checked kernel (a host restatement
+has no self-check to fail) and counts as clean; GpuOps always has one.
 """
 from __future__ import annotations
 
@@ -33,6 +37,9 @@ import radixsort as rs
 
 # total sample budget over all ranks (rsort_multi.cpp kSampleBudget)
 SAMPLE_BUDGET = 1 << 20
+# words of the step-5 row: the bucket counts (room for 2 * MAX_RANKS buckets, whatever a rank's splitters
+# gave it -- a rank whose sample sort failed may count other buckets than its peers), capacity, status
+ROW_BUCKETS = 2 * rs.MAX_RANKS
 # keys per message of one exchange round (1 GiB of u32): the RCCL of this image (2.26, ROCm 7;
 # torch 2.10) silently leaves the second half of an all_to_all message of >= 2 GiB unwritten
 # (dev/a2a_lab.py: 1 GiB arrives whole, 2 GiB - 4 B does not)
@@ -46,6 +53,7 @@ class GpuOps:
     def __init__(self, device):
         self.device = device
         self._ws = None
+        self._check = {}  # step -> reader of the check word that step's last run left in the workspace
 
     def _workspace(self, nbytes):
         if self._ws is None or self._ws.numel() < nbytes:
@@ -57,7 +65,9 @@ class GpuOps:
 
     def sort_keys(self, keys):
         p = rs.plan(keys.numel(), 8, False)
-        rs.sort_device(keys, keys, 8, ws=self._workspace(p.workspace_bytes), plan_=p, hybrid=False)
+        ws = self._workspace(p.workspace_bytes)
+        rs.sort_device(keys, keys, 8, ws=ws, plan_=p, hybrid=False)
+        self._check["sample"] = lambda: rs.plan_check(p, ws)
         return keys
 
     def partition(self, keys, vals, splitters):
@@ -67,16 +77,26 @@ class GpuOps:
         vo = torch.empty_like(vals) if vals is not None else None
         starts = torch.empty(nb + 1, dtype=torch.int32, device=self.device)
         need = int(rs._lib().rsort_partition_workspace_size(n, nb, 1 if vals is not None else 0))
-        rs.partition_device(keys, ko, splitters, starts, vals_in=vals, vals_out=vo, ws=self._workspace(need))
+        ws = self._workspace(need)
+        rs.partition_device(keys, ko, splitters, starts, vals_in=vals, vals_out=vo, ws=ws)
+        self._check["partition"] = lambda: rs.partition_check(n, nb, vals is not None, ws)
         return ko, vo, starts
 
     def sort(self, keys, vals, k_bits):
         """In place."""
         n = keys.numel()
         p = rs.plan(n, k_bits, vals is not None)
-        rs.sort_device(keys, keys, k_bits, vals_in=vals, vals_out=vals, ws=self._workspace(p.workspace_bytes),
+        ws = self._workspace(p.workspace_bytes)
+        rs.sort_device(keys, keys, k_bits, vals_in=vals, vals_out=vals, ws=ws,
                        plan_=p, hybrid=False)  # (a rank's keys cover 1 / N of the key space)
+        self._check["sort"] = lambda: rs.plan_check(p, ws)
         return keys, vals
+
+    def check(self, step):
+        """The self-check flags of the last "sample", "partition" or "sort" step (synchronises): read before the
+        next step reuses the workspace. 0 for a step that has not run."""
+        read = self._check.pop(step, None)
+        return read() if read is not None else 0
 
 
 def host_transport(group=None) -> "rs.HostTransport":
@@ -118,7 +138,9 @@ def dist_sort(keys, k_bits=8, vals=None, ops=None, group=None, capacity=None):
     Collectives run on the tensors' device with RCCL ("nccl"); with the gloo backend (tests:
     several ranks sharing one GPU, or CPU-only ranks) they run on host copies. capacity: the
     most keys this rank may receive (None: no limit); rs.RSortError(RSORT_ERR_CAPACITY) on every
-    rank alike when any rank's limit would be exceeded."""
+    rank alike when any rank's limit would be exceeded. rs.RSortError(RSORT_ERR_CHECK) on every rank alike, before
+    any key moves, when any rank's sample sort or partition failed its on-device self-check; on one rank alone when
+    its final sort did (the other ranks' slices are right)."""
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     if ops is None:
@@ -133,6 +155,9 @@ def dist_sort(keys, k_bits=8, vals=None, ops=None, group=None, capacity=None):
         dist.all_gather(out, t, group=group)
         return torch.stack(out)
 
+    # (an ops without self-checks -- no device kernels behind it -- reports every step clean)
+    check = getattr(ops, "check", None) or (lambda step: 0)
+
     n = keys.numel()
     # 1. key counts -> sampling plan
     n_all = all_gather(torch.tensor([n], dtype=torch.int64)).cpu().numpy().reshape(-1)
@@ -143,8 +168,10 @@ def dist_sort(keys, k_bits=8, vals=None, ops=None, group=None, capacity=None):
     q = [0] * (world - 1)
     hot = None
     gathered = all_gather(row).reshape(-1)
+    failed = 0  # this rank's sample sort or partition failed its self-check: told to every rank in step 5
     if world > 1 and sp.total > 0:
         srt = ops.sort_keys(gathered.to(dev))
+        failed |= check("sample")
         srt = srt.cpu().numpy().view(np.uint32)[:sp.total]  # (the rows' padding sorts after the samples)
         qpos = [rs.multi_quantile_index(sp, i) for i in range(1, world)]
         q = [int(srt[i]) for i in qpos]
@@ -153,13 +180,20 @@ def dist_sort(keys, k_bits=8, vals=None, ops=None, group=None, capacity=None):
 
     # 3-4. stable partition into the splitters' buckets
     pk, pv, starts = ops.partition(keys, vals, spl.splitters)
+    failed |= check("partition")
     st = starts.to(torch.int64).cpu().numpy()
     cnt = (st[1:] - st[:-1]).astype(np.int64)
     cap = NO_LIMIT if capacity is None else int(capacity)
 
-    # 5. count matrix + capacities -> the exchange plan (identical on every rank)
-    rows = all_gather(torch.from_numpy(np.concatenate([cnt, [cap]]).astype(np.int64))).cpu().numpy()
-    xp = rs.multi_exchange_plan(world, rank, rows[:, :-1], spl, rows[:, -1])
+    # 5. count matrix + capacities + statuses -> the exchange plan (identical on every rank)
+    mine = np.zeros(ROW_BUCKETS + 2, np.int64)
+    mine[:cnt.size] = cnt
+    mine[-2:] = cap, (rs.RSORT_ERR_CHECK if failed else rs.RSORT_OK)
+    rows = all_gather(torch.from_numpy(mine)).cpu().numpy()
+    for r in range(world):  # the lowest failed rank's status, on every rank together
+        if rows[r, -1] != rs.RSORT_OK:
+            raise rs.RSortError(int(rows[r, -1]), f"dist_sort: rank {r}'s sample sort or partition")
+    xp = rs.multi_exchange_plan(world, rank, rows[:, :cnt.size], spl, rows[:, -2])
 
     # 6. the exchange into source-rank order (stability)
     send_off, send_cnt = list(xp.send_off)[:world], list(xp.send_cnt)[:world]
@@ -193,4 +227,6 @@ def dist_sort(keys, k_bits=8, vals=None, ops=None, group=None, capacity=None):
 
     # 7. local LSD sort of the received keys
     ok, ov = ops.sort(rk, rv, k_bits)
+    if check("sort"):  # (this rank's own: the exchange is over, nobody waits for it)
+        raise rs.RSortError(rs.RSORT_ERR_CHECK, "dist_sort: the local sort")
     return ok, ov, int(xp.offset)

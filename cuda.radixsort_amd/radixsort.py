@@ -36,6 +36,7 @@ PKG = Path(__file__).resolve().parent
 LIB_PATH = PKG / "librsort.so"
 
 RSORT_OK = 0
+RSORT_ERR_CHECK = 11
 STATUS_NAMES = {0: "RSORT_OK", 1: "RSORT_ERR_ARG", 2: "RSORT_ERR_BITS", 3: "RSORT_ERR_SIZE",
                 4: "RSORT_ERR_ALIGN", 5: "RSORT_ERR_ALLOC", 6: "RSORT_ERR_HIP",
                 7: "RSORT_ERR_WORKSPACE", 8: "RSORT_ERR_NODEV", 9: "RSORT_ERR_CAPACITY",
@@ -193,6 +194,8 @@ SIGNATURES = {
     "rsort_plan_features": ([_PP], _int),
     "rsort_inject_table_fault": ([_int], _int),
     "rsort_inject_rank_fault": ([_int], _int),
+    "rsort_inject_fault_window": ([_i64, _i64], _int),
+    "rsort_fault_window_calls": ([], _i64),
     "rsort_scatter_kernels_used": ([ctypes.c_char_p, _sz, _int], _sz),
     "rsort_scatter_kernels_known": ([ctypes.c_char_p, _sz], _sz),
     "rsort_profile_begin": ([], _int),
@@ -531,6 +534,24 @@ def rank_fault():
     """TEST HOOK (rsort_inject_rank_fault): the lane-ordered scatter kernels swap two ranks per digit in
     the slot their per-tile rank check reads (a broken lane order); the check must report it."""
     return _setting("rsort_inject_rank_fault", 1)
+
+
+@contextmanager
+def fault_window(first: int, count: int = 1):
+    """TEST HOOK (rsort_inject_fault_window): inside the block only the CALLING THREAD's sort calls numbered
+    first .. first + count - 1 (from 0 at entry; every sort the library runs through its LSD driver) see table_fault()
+    / rank_fault(), and what is no sort call (the partition, a single pass, the segmented sort) sees neither; the window
+    is cleared on exit. fault_window_calls() says how many sort calls have started."""
+    _check(_lib().rsort_inject_fault_window(int(first), int(count)), "rsort_inject_fault_window")
+    try:
+        yield
+    finally:
+        _lib().rsort_inject_fault_window(0, -1)
+
+
+def fault_window_calls() -> int:
+    """rsort_fault_window_calls: the sort calls this thread has started since it last set or cleared the window."""
+    return int(_lib().rsort_fault_window_calls())
 
 
 CHECK_TABLE, CHECK_RANK_ORDER = 1, 2
@@ -1141,8 +1162,19 @@ def topk_report(n: int, k: int, pairs: bool, ws, stream=None) -> dict:
     return {name: int(r[i]) for i, name in enumerate(TOPK_REPORT)}
 
 
+def topk_check(n: int, k: int, pairs: bool, ws, stream=None) -> int:
+    """report8[6] of rsort_topk_report for the last top-k call in `ws` (synchronises the stream): the self-checks of
+    the sort that call ran, CHECK_TABLE / CHECK_RANK_ORDER bits as plan_check gives them; 0 = clean, or no sort ran.
+    (Its own reader, like topk_rows_check: topk_report's dict is the select's six figures.)"""
+    r = (ctypes.c_int64 * 8)()
+    _check(_lib().rsort_topk_report(int(n), int(k), 1 if pairs else 0, _ptr(ws), r, _stream(stream)),
+           "rsort_topk_report")
+    return int(r[6])
+
+
 def topkByDevice(keys, k, largest=False, vals=None, indices=False, sorted=True):
-    """rsort_u32_topk over numpy host arrays: (keys_out, vals_out or None) of k elements. Synchronous."""
+    """rsort_u32_topk over numpy host arrays: (keys_out, vals_out or None) of k elements. Synchronous; raises
+    RSortError(RSORT_ERR_CHECK) when the sort the call ran failed a self-check."""
     keys = _host_u32(keys, None, "keys")
     n, k = keys.size, int(k)
     if vals is not None:

@@ -280,14 +280,20 @@ RSORT_API size_t rsort_topk_workspace_size(int64_t n, int64_t k, int pairs, int 
 RSORT_API int    rsort_u32_topk_device(const uint32_t *d_keys_in, const uint32_t *d_vals_in, int64_t n, int64_t k,
                                        int flags, uint32_t *d_keys_out, uint32_t *d_vals_out, void *d_workspace,
                                        size_t workspace_bytes, void *stream);
-/* host -> host, synchronous, library-owned cached workspace (as rsort_u32). RSORT_ERR_NODEV without a device. */
+/* host -> host, synchronous, library-owned cached workspace (as rsort_u32). RSORT_ERR_NODEV without a device;
+ * RSORT_ERR_CHECK when the sort the call ran failed a self-check (report8[6] below is not 0). */
 RSORT_API int    rsort_u32_topk(const uint32_t *keys, const uint32_t *vals, int64_t n, int64_t k, int flags,
                                 uint32_t *keys_out, uint32_t *vals_out);
 /* After the call has completed on `stream` in `d_workspace`: report8[0] = the route taken (RSORT_TOPK_SELECT or
  * RSORT_TOPK_SORT), [1] = the k-th key (as stored, not xor-ed), [2] = the selected entries strictly before it in
  * the order, [3] = the entries equal to it that were taken, [4] = the entries equal to it in the input, [5] = the
- * candidates left after the first digit, [6], [7] = 0 (reserved). On the SORT route [0] and [1] are filled and
- * [2..5] are -1. All 0 for k == 0. Synchronises the stream, as rsort_segmented_check does. */
+ * candidates left after the first digit, [6] = the self-checks of the sort the call ran, as rsort_plan_check reports
+ * them (RSORT_CHECK_* bits, 0 = clean): the finishing sort of the k entries on the SELECT route, the whole sort on
+ * the SORT route; 0 when the call ran no sort (RSORT_TOPK_UNSORTED on the SELECT route), whatever the workspace held
+ * before; [7] = 0 (reserved). On the SORT route [0], [1] and [6] are filled and [2..5] are -1. All 0 for k == 0.
+ * The device entry is stream-ordered and cannot return the check: this report is the only way to learn of it.
+ * n, k and pairs must be the call's (the sort's workspace lies behind regions they size). Synchronises the stream,
+ * as rsort_segmented_check does. */
 RSORT_API int    rsort_topk_report(int64_t n, int64_t k, int pairs, const void *d_workspace, int64_t *report8,
                                    void *stream);
 /* Process-wide, like rsort_set_hybrid; returns the old route, or -RSORT_ERR_ARG for an unknown one (nothing changes). */
@@ -393,7 +399,9 @@ RSORT_API int rsort_pass_histogram(const rsort_plan *plan, const uint32_t *d_key
 RSORT_API int rsort_pass_scan(const rsort_plan *plan, uint32_t *d_table, uint32_t *d_block_sums,
                               void *stream);
 /* Fused block-local sort + global rank + scatter of one pass (vals may be NULL when
- * plan->pairs == 0). d_table is the scanned table of the same pass. */
+ * plan->pairs == 0). d_table is the scanned table of the same pass.
+ * rsort_pass_scatter and rsort_pass_local_sort take no workspace and so have no check word: the self-checks that
+ * rsort_plan_check reports for a whole sort are not recorded for a single pass, and no call returns them. */
 RSORT_API int rsort_pass_scatter(const rsort_plan *plan, const uint32_t *d_keys_in,
                                  const uint32_t *d_vals_in, uint32_t *d_keys_out,
                                  uint32_t *d_vals_out, int shift, const uint32_t *d_table,
@@ -540,6 +548,19 @@ RSORT_API int rsort_inject_table_fault(int enable);
  * of order), and the check catches it: rsort_plan_check reports bit 1 (RSORT_CHECK_RANK_ORDER), the host
  * entries return RSORT_ERR_CHECK. Process-wide; returns the previous setting. */
 RSORT_API int rsort_inject_rank_fault(int enable);
+/* TEST HOOK (never set in production): a window of the CALLING THREAD over the two hooks above, so a test can fault
+ * one sort of an entry that runs several (the multi-GPU sort: sample sort, lower half, upper half) and none of its
+ * neighbours. The thread's sort calls -- every sort the library runs through its LSD driver, whichever entry
+ * makes it -- are numbered from 0 once the window is set; only calls first .. first + count - 1 see
+ * rsort_inject_table_fault / rsort_inject_rank_fault, the others run as with both cleared. count < 0 clears the
+ * window (the default): every call sees the hooks. The partition's scatter, a single pass (rsort_pass_*) and the
+ * segmented sort are not sort calls and lie in no window: they follow the process-wide hooks while the calling thread
+ * has no window, as ever, and see neither hook while it has one (so a rank of the multi-GPU sort can fault one of its
+ * sorts and not its partition). RSORT_ERR_ARG for first < 0 with count >= 0.
+ * rsort_fault_window_calls: the sort calls the calling thread has started since it last set (or cleared) the
+ * window -- what a test asserts its numbering with. */
+RSORT_API int     rsort_inject_fault_window(int64_t first, int64_t count);
+RSORT_API int64_t rsort_fault_window_calls(void);
 /* The workgroups rsort_u32_segmented_device launches each of its four kernels with, for a call with these
  * arguments on the current device under the current process settings (rsort_set_rank_algo, the limit below):
  * grids[0..3] = the one-wave kernel (four segments per workgroup), the small workgroup shape, the large one, the
@@ -588,7 +609,7 @@ RSORT_API int rsort_partition_device(const uint32_t *d_keys_in, const uint32_t *
 /* After rsort_partition_device(n, num_buckets, pairs) has completed on `stream` in `d_workspace`: its
  * on-device self-check, as rsort_plan_check reports a sort's (bit 1: its scatter's rank check failed).
  * Synchronises the stream. rsort_u32_multi* reads it after every partition and returns RSORT_ERR_CHECK
- * on every rank when any rank's failed. */
+ * on every rank when any rank's failed (as it does for its sample sort; its local sorts' checks are the rank's own). */
 RSORT_API int rsort_partition_check(int64_t n, int num_buckets, int pairs, const void *d_workspace, int *flags,
                                     void *stream);
 /* Histogram of the top `top_bits` (1..12) bits of n keys into d_hist[2^top_bits] (u32,
@@ -692,8 +713,9 @@ RSORT_API int rsort_multi_exchange_rounds(int64_t max_message, int64_t limit, in
  * bucket of its own for each hot quantile key, so a run of equal keys is split across
  * ranks -> stable partition -> all-gather of the bucket counts and capacities -> the exchange
  * plan (the same on every rank) -> one exchange (own range by a device copy, the rest point to
- * point in rounds of <= 2^28 keys per message) -> local LSD sort. Synchronises `stream` four
- * times (counts are needed on the host).
+ * point in rounds of <= 2^28 keys per message) -> local LSD sort. Synchronises `stream` five
+ * times: four for counts the host needs, and once at the end for the local sorts' self-checks, so the call
+ * returns only when its local sort has finished (it is not asynchronous in its last step).
  * capacity: room in d_keys_out / d_vals_out. RSORT_ERR_CAPACITY when ANY rank would receive more
  * than its capacity: every rank returns it, before any key moves (balanced output needs about
  * total / world plus the sampling error, ~0.1 %). Up to RSORT_MAX_RANKS ranks.
@@ -703,7 +725,14 @@ RSORT_API int rsort_multi_exchange_rounds(int64_t max_message, int64_t limit, in
  * waiting in a collective (a rank that dies instead is caught by the RCCL timeout below). Only a transport that cannot run at all (NULL
  * transport or workspace, a workspace smaller than the collectives' control buffers) returns at
  * once on that rank. Failures in or after the exchange (the exchange itself, the local sort) are
- * the failing rank's own. */
+ * the failing rank's own.
+ * Self-checks (rsort_plan_check's bits): every sort and the partition this call runs is checked, and a failed
+ * check is RSORT_ERR_CHECK, never a silent RSORT_OK. The sample sort's and the partition's are read before the
+ * exchange and travel like any other failure there: every rank returns RSORT_ERR_CHECK together, before any key
+ * moves. The local sorts' -- each half's under the overlap, the direct sort's at world 1 -- are copied into the
+ * control area right behind each sort (the halves share one sort workspace, so the upper half's sort would clear
+ * what the lower half's recorded) and read at the end: RSORT_ERR_CHECK on that rank alone, whose output is then not
+ * trustworthy; the other ranks' slices are right. */
 RSORT_API size_t rsort_multi_workspace_size(int64_t n, int64_t capacity, int k_bits, int pairs, int world);
 /* Over an RCCL communicator (`nccl_comm` is an ncclComm_t; RCCL result codes are all checked,
  * RSORT_ERR_COMM on failure). Every RCCL call is bounded: the sort waits for each collective and

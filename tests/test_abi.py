@@ -33,6 +33,81 @@ def test_every_declared_symbol_is_exported_and_bound():
     assert set(rs.SIGNATURES) == set(declared)
 
 
+# Where a failed on-device self-check (rsort_plan_check's bits) of each entry reaches its caller: a closed table, one
+# row per RSORT_API function. The kernels that record a check are the scatter kernels (sorts, the partition), the
+# raw-table passes, the hybrid bucket kernel and the segmented sort's kernels.
+#   NONE       launches no checked kernel (pure, a setting, a reader, or kernels that check nothing)
+#   reader: F  stream-ordered: returns before the device has run, F reads the check afterwards
+#   ERR_CHECK  waits for the device and returns RSORT_ERR_CHECK itself
+#   (NOT, s)   none, documented: s is the sentence of rsort.h that says so
+# tests/test_gpu_check_entries.py and tests/test_gpu_check.py drive every reader and ERR_CHECK row on the device.
+NONE, ERR_CHECK = "launches no checked kernel", "returns RSORT_ERR_CHECK"
+_PASS_SENTENCE = ("rsort_pass_scatter and rsort_pass_local_sort take no workspace and so have no check word: the "
+                  "self-checks that rsort_plan_check reports for a whole sort are not recorded for a single pass, and "
+                  "no call returns them.")
+NOT = ("none, documented", _PASS_SENTENCE)
+CHECK_REACHES_CALLER = {
+    "rsort_status_string": NONE, "rsort_version": NONE, "rsort_plan_make": NONE, "rsort_workspace_size": NONE,
+    "rsort_u32_device": "reader: rsort_plan_check", "rsort_u32_pairs_device": "reader: rsort_plan_check",
+    "rsort_sort_planned_ex": "reader: rsort_plan_check", "rsort_sort_planned": "reader: rsort_plan_check",
+    "rsort_u32": ERR_CHECK, "rsort_u32_ex": ERR_CHECK, "rsort_u32_pairs": ERR_CHECK,
+    "rsort_segmented_capacity": NONE, "rsort_segmented_workspace_size": NONE,
+    "rsort_u32_segmented_device": "reader: rsort_segmented_check", "rsort_segmented_check": NONE,
+    "rsort_u32_segmented": ERR_CHECK,
+    "rsort_topk_workspace_size": NONE, "rsort_u32_topk_device": "reader: rsort_topk_report",
+    "rsort_u32_topk": ERR_CHECK, "rsort_topk_report": NONE, "rsort_set_topk_route": NONE,
+    "rsort_get_topk_route": NONE, "rsort_topk_auto_limit": NONE, "rsort_topk_grids": NONE,
+    "rsort_set_topk_grid_limit": NONE,
+    "rsort_topk_rows_workspace_size": NONE, "rsort_u32_topk_rows_device": "reader: rsort_topk_rows_check",
+    "rsort_u32_topk_rows": ERR_CHECK, "rsort_topk_rows_check": NONE, "rsort_topk_rows_grids": NONE,
+    "rsort_set_topk_rows_grid_limit": NONE,
+    "rsort_pass_histogram": NONE, "rsort_pass_scan": NONE, "rsort_pass_scatter": NOT, "rsort_pass_local_sort": NOT,
+    "rsort_set_rank_algo": NONE, "rsort_get_rank_algo": NONE, "rsort_set_group_chunks": NONE,
+    "rsort_get_group_chunks": NONE, "rsort_set_hybrid": NONE, "rsort_get_hybrid": NONE,
+    "rsort_hybrid_capacity": NONE, "rsort_hybrid_kernel_info": NONE, "rsort_hybrid_range": NONE,
+    "rsort_hybrid_gate_threshold": NONE, "rsort_hybrid_report": NONE, "rsort_group_flags": NONE,
+    "rsort_cut_plan_stats": NONE, "rsort_plan_check": NONE, "rsort_plan_features": NONE,
+    "rsort_inject_table_fault": NONE, "rsort_inject_rank_fault": NONE, "rsort_inject_fault_window": NONE,
+    "rsort_fault_window_calls": NONE, "rsort_segmented_grids": NONE, "rsort_set_segmented_grid_limit": NONE,
+    "rsort_scatter_kernels_used": NONE, "rsort_scatter_kernels_known": NONE, "rsort_lane_order_probe": NONE,
+    "rsort_profile_begin": NONE, "rsort_profile_end": NONE,
+    "rsort_partition_workspace_size": NONE, "rsort_partition_device": "reader: rsort_partition_check",
+    "rsort_partition_check": NONE, "rsort_top_histogram": NONE, "rsort_top_histogram_sampled": NONE,
+    "rsort_multi_sample_plan": NONE, "rsort_sample_device": NONE, "rsort_multi_quantile_index": NONE,
+    "rsort_multi_splitters_make": NONE, "rsort_multi_splitters_make_hot": NONE, "rsort_multi_exchange_plan": NONE,
+    "rsort_multi_exchange_rounds": NONE, "rsort_multi_workspace_size": NONE,
+    "rsort_u32_multi": ERR_CHECK, "rsort_u32_multi_transport": ERR_CHECK,
+    "rsort_rccl_unique_id": NONE, "rsort_rccl_comm_init": NONE, "rsort_rccl_comm_destroy": NONE,
+    "rsort_set_comm_timeout": NONE, "rsort_set_multi_options": NONE, "rsort_multi_set_profiling": NONE,
+    "rsort_multi_last_stats": NONE, "rsort_multi_inject_failure": NONE, "rsort_set_exchange_piece": NONE,
+    "rsort_host_transport_wrap": NONE, "rsort_host_transport_free": NONE, "rsort_loopback_create": NONE,
+    "rsort_loopback_transport": NONE, "rsort_loopback_destroy": NONE,
+    "rsort_vendor_workspace_size": NONE, "rsort_u32_vendor_device": NONE, "rsort_u32_vendor": NONE,
+    "rsort_vendor_segmented_workspace_size": NONE, "rsort_u32_vendor_segmented_device": NONE,
+    "rsort_fingerprint_device": NONE, "rsort_gen_uniform": NONE, "rsort_gen_zipf": NONE, "rsort_gen_iota": NONE,
+}
+
+
+def test_every_entry_says_where_a_failed_self_check_goes():
+    """The table is closed: a declared function without a row fails, a row naming no declared function fails, every
+    reader named is itself declared and launches nothing checked, and a "none, documented" row quotes rsort.h."""
+    declared = set(_declared_symbols())
+    assert declared - set(CHECK_REACHES_CALLER) == set(), "declared in rsort.h, no row in the table"
+    assert set(CHECK_REACHES_CALLER) - declared == set(), "rows naming no declared function"
+    header = " ".join((ROOT / "include" / "rsort.h").read_text().replace("*", " ").split())
+    for name, how in CHECK_REACHES_CALLER.items():
+        if isinstance(how, tuple):
+            assert how[0] == "none, documented" and " ".join(how[1].split()) in header, name
+        elif how.startswith("reader: "):
+            reader = how[len("reader: "):]
+            assert reader in declared and CHECK_REACHES_CALLER[reader] == NONE, name
+        else:
+            assert how in (NONE, ERR_CHECK), name
+    # every host -> host and multi-GPU sorting entry waits for the device: it has no excuse not to return the check
+    waits = {n for n in declared if re.fullmatch(r"rsort_u32(_ex|_pairs|_segmented|_topk|_topk_rows|_multi\w*)?", n)}
+    assert waits == {n for n, how in CHECK_REACHES_CALLER.items() if how == ERR_CHECK}
+
+
 def test_status_strings():
     lib = rs._lib()
     for st in range(12):
@@ -228,3 +303,69 @@ def test_multi_workspace_holds_any_local_sort(n, world):
     sizes = {cap, cap // 2 + 1, n, 1 << 25, (1 << 24) + 5, 1 << 23, 3 << 22, 1 << 20, 1}
     need = max(rs.workspace_size(m, 8) for m in sizes if m <= cap)
     assert mw >= 4 * n + need, (mw, need)
+
+
+def _sort_call():
+    """One entry into the LSD driver that needs no device: an n = 0 sort (a numbered sort call that then does nothing)."""
+    assert rs._lib().rsort_u32_device(None, None, 0, 8, None, 0, None) == 0
+
+
+def test_fault_window_numbers_the_sort_calls_and_clears():
+    """rsort_inject_fault_window, host side: setting it (and clearing it) restarts the calling thread's count of sort
+    calls; rsort_fault_window_calls reads it; a negative first with a window is refused and changes nothing; the
+    context manager clears on exit, also when its block raises."""
+    lib = rs._lib()
+    assert lib.rsort_inject_fault_window(0, -1) == 0 and rs.fault_window_calls() == 0
+    _sort_call()
+    assert rs.fault_window_calls() == 1  # (counted with the window cleared too)
+    with rs.fault_window(1, 2):
+        assert rs.fault_window_calls() == 0
+        for i in range(4):
+            _sort_call()
+            assert rs.fault_window_calls() == i + 1
+        assert lib.rsort_inject_fault_window(-1, 1) == 1 and rs.fault_window_calls() == 4  # refused: nothing changes
+        with pytest.raises(rs.RSortError):
+            with rs.fault_window(-3, 0):
+                pass
+    assert rs.fault_window_calls() == 0  # cleared on exit: a new count
+    with pytest.raises(KeyError):
+        with rs.fault_window(0, 1):
+            _sort_call()
+            raise KeyError("from the block")
+    assert rs.fault_window_calls() == 0
+    # the pairs entry and the planned entries are sort calls too; a plan that is refused never enters the driver
+    assert lib.rsort_u32_pairs_device(None, None, None, None, 0, 8, None, 0, None) == 0
+    p = rs.plan(0, 8)
+    assert lib.rsort_sort_planned(ctypes.byref(p), None, None, None, None, None, 0, None) == 0
+    assert lib.rsort_sort_planned_ex(ctypes.byref(p), None, None, None, None, None, 0, None, 1) == 0
+    assert lib.rsort_u32_device(None, None, 10, 0, None, 0, None) == 2
+    assert rs.fault_window_calls() == 3
+
+
+def test_fault_window_is_thread_local():
+    """Two threads: each sets its own window and counts its own sort calls; neither sees the other's, and the main
+    thread's count is untouched."""
+    import threading
+    lib = rs._lib()
+    assert lib.rsort_inject_fault_window(0, -1) == 0
+    _sort_call()
+    seen, step = {}, threading.Barrier(2, timeout=30)
+
+    def run(name, calls):
+        with rs.fault_window(0, 1):
+            step.wait()  # both windows are set before either thread sorts
+            for _ in range(calls):
+                _sort_call()
+            step.wait()  # both have sorted before either reads
+            seen[name] = rs.fault_window_calls()
+            step.wait()
+        seen[name + " after"] = rs.fault_window_calls()
+
+    th = [threading.Thread(target=run, args=("a", 2)), threading.Thread(target=run, args=("b", 5))]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join(timeout=60)
+    assert not any(t.is_alive() for t in th)
+    assert seen == {"a": 2, "b": 5, "a after": 0, "b after": 0}
+    assert rs.fault_window_calls() == 1

@@ -35,7 +35,17 @@ def _t(a):
 
 
 class NumpyOps:
-    """CPU stand-in for multi.GpuOps with the kernels' exact semantics (test-only)."""
+    """CPU stand-in for multi.GpuOps with the kernels' exact semantics (test-only). fail: the steps ("sample",
+    "partition", "sort") whose on-device self-check this rank reports as failed (rs.CHECK_RANK_ORDER), as a GPU
+    whose sort broke its premise would; the step's output is computed as ever."""
+
+    def __init__(self, fail=()):
+        self.fail = set(fail)
+        self.ran = []
+
+    def check(self, step):
+        assert self.ran and self.ran[-1] == step, (step, self.ran)  # (read before the next step reuses the workspace)
+        return multi.rs.CHECK_RANK_ORDER if step in self.fail else 0
 
     def sample(self, keys, stride, count, row_len):
         # rsort_sample_device: key[min(n - 1, j * stride + stride / 2)] for j < count, then padding
@@ -47,9 +57,11 @@ class NumpyOps:
         return _t(out)
 
     def sort_keys(self, keys):
+        self.ran.append("sample")
         return _t(np.sort(_u32(keys)))
 
     def partition(self, keys, vals, splitters):
+        self.ran.append("partition")
         k = _u32(keys)
         # bucket = number of splitters <= key (the kernels' kDigitSplit digit)
         b = np.searchsorted(np.asarray(splitters, np.uint32), k, side="right")
@@ -59,6 +71,7 @@ class NumpyOps:
         return _t(k[order]), vo, torch.from_numpy(starts)
 
     def sort(self, keys, vals, k_bits):
+        self.ran.append("sort")
         if vals is None:
             return _t(oracle_sort(_u32(keys), k_bits)), None
         rk, rv = oracle_sort_pairs(_u32(keys), _u32(vals), k_bits)
@@ -160,6 +173,76 @@ def test_dist_sort_capacity_error_on_every_rank(tmp_path):
     world = 3
     mp.spawn(_cap_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
     assert [(tmp_path / f"r{r}").read_text() for r in range(world)] == ["9"] * world
+
+
+def _check_worker(rank, world, port, out_dir, step, bad_rank, pairs):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        keys, vals = _inputs(rank, 20_000, "zipf", pairs)
+        ops = NumpyOps(fail=(step,) if rank == bad_rank else ())
+        try:
+            ok, ov, off = multi.dist_sort(_t(keys), 8, vals=_t(vals) if pairs else None, ops=ops)
+            np.save(f"{out_dir}/k{rank}.npy", _u32(ok))
+            np.save(f"{out_dir}/o{rank}.npy", np.array([off], np.int64))
+            res = "ok"
+        except multi.rs.RSortError as e:
+            res = str(e.status)
+        (Path(out_dir) / f"r{rank}").write_text(res + " " + ",".join(ops.ran))
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("step", ["sample", "partition"])
+def test_dist_sort_failed_check_before_the_exchange_raises_on_every_rank(tmp_path, step):
+    """One rank's sample sort or partition reports a failed self-check (ops.check): its status travels in the
+    step-5 all-gather and EVERY rank raises RSORT_ERR_CHECK (11) together, before the exchange -- no rank runs its
+    final sort, none is left waiting (the test would hang otherwise)."""
+    world = 3
+    mp.spawn(_check_worker, args=(world, _free_port(), str(tmp_path), step, 1, False), nprocs=world, join=True)
+    assert [(tmp_path / f"r{r}").read_text() for r in range(world)] == ["11 sample,partition"] * world
+
+
+def test_dist_sort_failed_check_of_the_final_sort_raises_on_that_rank_alone(tmp_path):
+    """The final sort's self-check is the rank's own: rank 1 raises RSORT_ERR_CHECK, ranks 0 and 2 return their
+    slices of the oracle's order at their offsets."""
+    world = 3
+    mp.spawn(_check_worker, args=(world, _free_port(), str(tmp_path), "sort", 1, False), nprocs=world, join=True)
+    res = [(tmp_path / f"r{r}").read_text().split()[0] for r in range(world)]
+    assert res == ["ok", "11", "ok"]
+    want = oracle_sort(np.concatenate([_inputs(r, 20_000, "zipf", False)[0] for r in range(world)]), 8)
+    off0, off2 = (int(np.load(tmp_path / f"o{r}.npy")[0]) for r in (0, 2))
+    got0, got2 = (np.load(tmp_path / f"k{r}.npy") for r in (0, 2))
+    assert off0 == 0 and np.array_equal(got0, want[:got0.size])
+    assert off2 + got2.size == want.size and np.array_equal(got2, want[off2:])
+
+
+class NoCheckOps(NumpyOps):
+    """An ops object from before ops.check existed: no self-checks to report."""
+    check = None
+
+
+def _no_check_worker(rank, world, port, out_dir):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        keys, _ = _inputs(rank, 20_000, "zipf", False)
+        ok, _, off = multi.dist_sort(_t(keys), 8, ops=NoCheckOps(fail=("sample", "partition", "sort")))
+        np.save(f"{out_dir}/k{rank}.npy", _u32(ok))
+        np.save(f"{out_dir}/o{rank}.npy", np.array([off], np.int64))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_dist_sort_ops_without_a_check_method_counts_as_clean(tmp_path):
+    """dist_sort's ops interface is public: an ops object written before ops.check (a host restatement with no
+    device kernel behind it) still sorts, every step counted clean."""
+    world = 2
+    mp.spawn(_no_check_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
+    got = [np.load(tmp_path / f"k{r}.npy") for r in range(world)]
+    assert [int(np.load(tmp_path / f"o{r}.npy")[0]) for r in range(world)] == [0, got[0].size]
+    assert np.array_equal(np.concatenate(got), oracle_sort(
+        np.concatenate([_inputs(r, 20_000, "zipf", False)[0] for r in range(world)]), 8))
 
 
 def test_exchange_rounds_never_exceed_the_limit():

@@ -198,6 +198,52 @@ def test_report_entry_validates():
     assert lib.rsort_topk_report(10, 0, 1, None, r, None) == 0 and list(r) == [0] * 8
 
 
+class _NoStream:
+    """Stands in for a torch stream where there may be no GPU: the validation paths never use it."""
+    cuda_stream = None
+
+
+def test_noop_calls_report_a_clean_check_field():
+    """report8[6], the self-checks of the sort a call ran: 0 for a call that had nothing to do (k == 0), with no
+    workspace and no device; rs.topk_check is that field."""
+    lib = rs._lib()
+    for n, k in ((10, 0), (0, 0), ((1 << 32) - 1, 0)):
+        for pairs in (0, 1):
+            r = (ctypes.c_int64 * 8)(*([9] * 8))
+            assert lib.rsort_topk_report(n, k, pairs, None, r, None) == 0 and r[6] == 0 and r[7] == 0
+            assert rs.topk_check(n, k, bool(pairs), None, stream=_NoStream()) == 0
+    with pytest.raises(rs.RSortError) as e:
+        rs.topk_check(10, 11, False, None, stream=_NoStream())
+    assert e.value.status == 1
+
+
+class _Returns:
+    """The library with one entry replaced by a stub that returns `status`: what the Python mirror does with it."""
+
+    def __init__(self, lib, name, status):
+        self._lib, self._name, self._status, self.calls = lib, name, status, 0
+
+    def __getattr__(self, attr):
+        if attr != self._name:
+            return getattr(self._lib, attr)
+
+        def stub(*args):
+            self.calls += 1
+            return self._status
+        return stub
+
+
+def test_python_mirror_raises_on_a_check_status(monkeypatch):
+    """rs.topkByDevice raises RSortError(11) when rsort_u32_topk returns RSORT_ERR_CHECK (no device: the entry is a
+    stub here; tests/test_gpu_check_entries.py has the library return it)."""
+    fake = _Returns(rs._lib(), "rsort_u32_topk", rs.RSORT_ERR_CHECK)
+    monkeypatch.setattr(rs, "_LIB", fake)
+    with pytest.raises(rs.RSortError) as e:
+        rs.topkByDevice(np.arange(8, dtype=np.uint32), 3, indices=True)
+    assert e.value.status == 11 == rs.RSORT_ERR_CHECK and fake.calls == 1
+    assert "RSORT_ERR_CHECK" in str(e.value)
+
+
 def test_python_constants():
     assert (rs.TOPK_LARGEST, rs.TOPK_UNSORTED, rs.TOPK_INDICES) == (1, 2, 4)
     assert (rs.TOPK_AUTO, rs.TOPK_SELECT, rs.TOPK_SORT) == (0, 1, 2)

@@ -195,6 +195,23 @@ def test_check_entry_validates():
         assert rs.topk_rows_check(rows, cols, k, False, None, stream=_NoStream()) == (0, [0, 0, 0, 0])
 
 
+def test_python_mirror_raises_on_a_check_status(monkeypatch):
+    """rs.topkRowsByDevice raises RSortError(11) when rsort_u32_topk_rows returns RSORT_ERR_CHECK (no device: the
+    entry is a stub here; tests/test_gpu_check_entries.py has the library return it)."""
+    real, calls = rs._lib(), []
+
+    class Fake:
+        def __getattr__(self, attr):
+            if attr != "rsort_u32_topk_rows":
+                return getattr(real, attr)
+            return lambda *args: calls.append(args) or rs.RSORT_ERR_CHECK
+
+    monkeypatch.setattr(rs, "_LIB", Fake())
+    with pytest.raises(rs.RSortError) as e:
+        rs.topkRowsByDevice(np.arange(12, dtype=np.uint32).reshape(3, 4), 2, largest=True)
+    assert e.value.status == 11 == rs.RSORT_ERR_CHECK and len(calls) == 1
+
+
 def test_python_wrapper_rejects_bad_tensors():
     x = torch.zeros((4, 10), dtype=torch.int32)
     with pytest.raises(TypeError):
